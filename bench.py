@@ -10,13 +10,24 @@ the counter block (and the timing max).  `python bench.py --gpus N` without a
 torch.distributed launcher spawns the N rank processes itself, before anything
 in this process touches the HIP runtime.
 
-Prints ONE JSON line (rank 0) with roofline, cpu_baseline and parity objects.
-`parity` is the full-scale bit-exactness check: the CPU restatement (oracle/)
-runs the same stream on a flow-group sample (1/--parity-div of the address
+Prints ONE JSON line (rank 0).  A plain run does what the headline figure needs
+and no more: set-up, warm-up, the --steps timed steps of the configuration, the
+line (value, ms_per_step, the roofline of the same timed steps from their HIP
+events).  --dump-outputs DIR also writes the records the last timed step returned
+(DIR/records.npy, see dump_outputs).  Config 2's steps run in blocks of STEP_BLOCK
+whose batches are generated on the device before the block's clock starts and
+released after it stops, so --steps may be in the hundreds: device memory holds one
+block and the elapsed time is the blocks' sum.  Everything else is behind --full: the
+cpu_baseline and parity objects, config 2's long-horizon continuation, the other
+configurations ("configs") and config 4's host->device leg.
+
+`parity` (--full) is the full-scale bit-exactness check: the CPU restatement (oracle/)
+runs the same stream on a flow-group sample (every pair at N=1 up to 64 steps, 1 pair in
+ceil(steps / 64) beyond, or 1/--parity-div of the address
 pairs: whole flow groups, so a sampled run of the stateful path is exact) and
 every sampled packet's GPU record, plus every CT entry of the sampled pairs at
 the end, must equal the oracle's.  Every rank checks its own partition and the
-counts are summed over ranks.  The line also carries "configs": at N=1 the other
+counts are summed over ranks.  With --full the line also carries "configs": at N=1 the other
 BASELINE configurations measured the same way (config 1 XDP prefilter, config 3
 service LB, config 4 full pipeline over raw frames — device-resident and with
 the host->device copy of the frames —, config 5 IPv6 pipeline, and the endpoint
@@ -271,42 +282,66 @@ class StandIn:
 
 
 # ----------------------------------------------------------------------------- timing
-def timed(B, run_step, W, K, world=1, ranged=False):
+def timed(B, run_step, W, K, world=1, ranged=False, chunk=None, before=None, after=None):
     """W untimed warm-up steps, then K steps bracketed by barrier + synchronize,
     with the verdict counter sink and the launch profiler on (ranged: run_step(a, b)
-    runs steps a..b-1 in one call).  Returns (elapsed_s (max over ranks), counters
-    (summed over ranks), local counters, {kernel: (launches, total_ms)})."""
+    runs steps a..b-1 in one call).  With `chunk`, the steps run in blocks of at most
+    `chunk`: before(a, b) makes the inputs of steps a..b-1 resident and after(a, b)
+    releases them, both outside the clock, so that a run of any length holds one
+    block in device memory; each block of timed steps is bracketed on its own
+    (barrier + synchronize before, synchronize after) and the elapsed time is the
+    blocks' sum.  At N>1 the figure is then the largest rank's sum of its block
+    times, which for K <= chunk is the single bracketed interval it was without
+    blocks.  Returns (elapsed_s (max over ranks),
+    counters (summed over ranks), local counters, {kernel: (launches, total_ms)})."""
     import torch
     import torch.distributed as dist
-    if ranged:
-        run_step(0, W)
-    else:
-        for s in range(W):
-            run_step(s)
+
+    def blocks(a, b):
+        """[a, b) cut into pieces of at most `chunk` steps (one piece without `chunk`)."""
+        size = chunk or b - a
+        return [(x, min(x + size, b)) for x in range(a, b, size)] if b > a else []
+    for a, b in blocks(0, W):
+        if before:
+            before(a, b)
+        if ranged:
+            run_step(a, b)
+        else:
+            for s in range(a, b):
+                run_step(s)
+        B.sync()
+        if after:
+            after(a, b)
     B.sync()
     B.begin()
-    if world > 1:
-        dist.barrier()
-    B.sync()
-    t0 = time.perf_counter()
     host = 0.0                                          # time inside the calls (host enqueue work + waits)
-    if ranged:
-        run_step(W, W + K)
-    else:
-        for s in range(W, W + K):
-            h0 = time.perf_counter()
-            run_step(s)
-            host += time.perf_counter() - h0
-    B.sync()
-    t1 = time.perf_counter()
+    elapsed = 0.0
+    for a, b in blocks(W, W + K):
+        if before:
+            before(a, b)
+        if world > 1:
+            dist.barrier()
+        B.sync()
+        t0 = time.perf_counter()
+        if ranged:
+            run_step(a, b)
+        else:
+            for s in range(a, b):
+                h0 = time.perf_counter()
+                run_step(s)
+                host += time.perf_counter() - h0
+        B.sync()
+        elapsed += time.perf_counter() - t0
+        if after:
+            after(a, b)
     if not ranged:
-        log(f"host time inside the classify calls: {host / K * 1e3:.3f} ms/step of {(t1 - t0) / K * 1e3:.3f}")
+        log(f"host time inside the classify calls: {host / K * 1e3:.3f} ms/step of {elapsed / K * 1e3:.3f}")
     if world > 1:
         dist.barrier()
     counters, kern = B.end()
     local = counters.clone()
-    B.local_elapsed = t1 - t0
-    tt = torch.tensor([t1 - t0], dtype=torch.float64, device=B.dev)
+    B.local_elapsed = elapsed
+    tt = torch.tensor([elapsed], dtype=torch.float64, device=B.dev)
     B.allreduce_ms = None
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -382,6 +417,36 @@ def cpu_loop(fn, seconds):
         done += fn()
         tt += time.perf_counter() - a
     return done, tt
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 48 << 20          # records + row indices of one dump stay below this (the limit is 64 MB)
+
+
+def dump_outputs(args, name, t):
+    """--dump-outputs DIR: the record tensor `t` (rows x bytes, uint8) that the caller
+    of the timed path received from its last timed step -> DIR/<name>.npy as float32,
+    one column per record byte (exact).  Where all rows would exceed DUMP_BYTES, a
+    fixed seeded sample of the rows (ascending) is written, and their row numbers
+    beside it as DIR/<name>_rows.npy (float64).  The inputs are seeded, so two runs
+    with the same arguments write the same rows of the same stream.  Ranks other
+    than 0 write <name>_rank<r>.npy."""
+    if not args.dump_outputs:
+        return
+    import torch
+    rank = int(os.environ.get("RANK", "0"))
+    if rank:
+        name = f"{name}_rank{rank}"
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    t = t.reshape(t.shape[0], -1)
+    n, width = int(t.shape[0]), int(t.shape[1])
+    rows = DUMP_BYTES // (width * 4 + 8)
+    if n > rows:
+        idx = np.sort(np.random.default_rng(0x6f75).choice(n, rows, replace=False))
+        t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(args.dump_outputs, name + "_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    log(f"dumped {min(n, rows)} of {n} records of the last timed step to {args.dump_outputs}/{name}.npy")
 
 
 # ----------------------------------------------------------------------------- parity bookkeeping
@@ -506,45 +571,76 @@ def bench_config2(args, B, rank, world, local_world=1):
     # timed steps on the same datapath, timed on their own, into the LRU sweeps a node
     # reaches once its CT holds max_entries (not with --pipeline: the continuation
     # runs through dp.ingress only, so the steps the device ran are exactly W + K)
-    L = max(args.long_steps, W + K) if world == 1 and not args.pipeline else W + K
-    rk, rv = st.reply_ct_entries(S0 + L)
+    H = max(args.long_steps, W + K) if world == 1 and not args.pipeline else W + K
+    # a plain run stops after the timed steps; its CT still starts with the reply entries of
+    # the whole horizon, so the timed steps see the same table with and without --full
+    L = H if args.full else W + K
+    rk, rv = st.reply_ct_entries(S0 + H)
     sc.maps["cilium_ct4_global"].keys, sc.maps["cilium_ct4_global"].vals = rk, rv
     ct_names = ct_local_split(sc, P, ct_max) if args.ct_local else ["cilium_ct4_global"]
     log(f"rank {rank}: tables {sum(m.n() for m in sc.maps.values())} entries, {len(rk)} pre-inserted CT, "
         f"{len(st.own)} owned pairs ({time.time() - t0:.1f}s)")
     dp = B.datapath(sc)
-    batches, ps = [], []
-    for s in range(L):
-        cols, p, n = st.step(S0 + s)
-        batches.append(ColBatch(cols, n, B.dev))
-        ps.append(p)
-    # one output buffer per step: the parity leg reads every step's records afterwards
-    outs = [torch.empty((b.n, 8), dtype=torch.uint8, device=B.dev) for b in batches]
-    B.sync()
-    log(f"rank {rank}: generated {L} steps ({time.time() - t0:.1f}s)")
+    t_loaded = time.time() - t0
+    log(f"rank {rank}: datapath loaded ({t_loaded:.1f}s)")
+    # The steps run in blocks of STEP_BLOCK: a block's batches and output buffers are
+    # generated on the device before its clock starts and released after it stops, so
+    # a run of any --steps holds one block in device memory.  The parity leg (--full)
+    # keeps what it compares afterwards: every step's sampled packets and their records
+    # (the whole step when the sample is every pair).
+    par_ctx = None if args.no_cpu else parity_sample2(args, st, world, local_world, L)
+    batches, ps, outs, kept, n_of = {}, {}, {}, {}, {}
+
+    gen = [0.0]                                          # seconds spent generating batches, all blocks
+
+    def before(a, b):
+        g0 = time.perf_counter()
+        for s in range(a, b):
+            cols, p, n = st.step(S0 + s)
+            batches[s], ps[s], n_of[s] = ColBatch(cols, n, B.dev), p, n
+            outs[s] = torch.empty((n, 8), dtype=torch.uint8, device=B.dev)
+        B.sync()
+        gen[0] += time.perf_counter() - g0
+
+    def after(a, b):
+        for s in range(a, b):
+            if par_ctx is not None:
+                kept[s] = parity_keep(par_ctx, batches[s].cdict, ps[s], outs[s], s == W)
+            if s != W + K - 1 or not args.dump_outputs:
+                del outs[s]
+            del batches[s], ps[s]
     now = sc.now
+    blk = dict(chunk=STEP_BLOCK, before=before, after=after)
     if not args.pipeline:
-        elapsed, c, lc, kern = timed(B, lambda s: dp.ingress(batches[s], now + s, out=outs[s]), W, K, world)
+        elapsed, c, lc, kern = timed(B, lambda s: dp.ingress(batches[s], now + s, out=outs[s]), W, K, world, **blk)
     else:
         # the stream of batches through gf_policy_ingress_classify_batches: batch s+1's
         # schedule is built on a second stream while handle_policy of batch s runs
         # (measured slower: the overlapped kernels share the memory system)
-        elapsed, c, lc, kern = timed(B, lambda a, b: dp.ingress_batches(batches[a:b], [now + s for s in range(a, b)],
-                                                                         outs[a:b]), W, K, world, ranged=True)
+        elapsed, c, lc, kern = timed(B, lambda a, b: dp.ingress_batches(
+            [batches[s] for s in range(a, b)], [now + s for s in range(a, b)], [outs[s] for s in range(a, b)]),
+            W, K, world, ranged=True, **blk)
+    log(f"rank {rank}: ran {W} + {K} steps ({time.time() - t0:.1f}s)")
     total_pkts = int(c[268])
+    if args.dump_outputs:
+        dump_outputs(args, "records", outs.pop(W + K - 1))
     wr = getattr(B, "wr", None)                          # GF_WRSTATS builds: writes by source, timed steps
     long_h = None
     if L > W + K:
         C_ = L - W - K
         el2, c2, _, kern2 = timed(B, lambda s: dp.ingress(batches[W + K + s], now + W + K + s, out=outs[W + K + s]),
-                                  0, C_, world)
+                                  0, C_, world, chunk=STEP_BLOCK, before=lambda a, b: before(W + K + a, W + K + b),
+                                  after=lambda a, b: after(W + K + a, W + K + b))
         lp = total_pkts + int(c2[268])
         long_h = {"steps": K + C_, "after_warmup": W, "mpps": round(lp / (elapsed + el2) / 1e6, 3),
                   "ms_per_step": round((elapsed + el2) / (K + C_) * 1e3, 4),
                   "continuation": {"steps": C_, "mpps": round(int(c2[268]) / el2 / 1e6, 3),
                                    "kernels_ms_per_step": kms(kern2, C_)}}
         log(f"long horizon: {long_h['mpps']} Mpps over {K + C_} steps (continuation {long_h['continuation']['mpps']})")
-    local_pkts = sum(batches[s].n for s in range(W, W + K))
+    # the set-up time up to the last generated batch, as if all L had been generated before the
+    # first step (tools/n8_projection.py reads this line): tables, datapath, then the blocks' generation
+    log(f"rank {rank}: generated {L} steps ({t_loaded + gen[0]:.1f}s)")
+    local_pkts = sum(n_of[s] for s in range(W, W + K))
     if not os.environ.get("GPUFLOW_DIAG_LIB"):
         assert int(lc[268]) == local_pkts, (int(lc[268]), local_pkts)
     # roofline of the dominant kernel (k_ing_groups), this rank
@@ -560,7 +656,7 @@ def bench_config2(args, B, rank, world, local_world=1):
     cpu = par = None
     if not args.no_cpu:
         # every rank checks its own flow groups; the CPU baseline is rank 0's at N=1 only
-        cpu, par = oracle_config2(args, B, sc, st, dp, batches, ps, outs, W, K, world, local_world, L, ct_names)
+        cpu, par = oracle_config2(args, B, sc, dp, par_ctx, kept, W, K, world, L, ct_names)
         if world > 1:
             cpu = None
     par = reduce_parity(B, par, rank, world)
@@ -583,7 +679,7 @@ def bench_config2(args, B, rank, world, local_world=1):
             "workload": "config2: bpf_lxc ingress handle_policy (ct_lookup4 + policy_can_access), steady-state "
                         "stream, 4M new flows/step (16M active), 256 endpoints, 4352 identities"
                         + (f", per-endpoint CT maps (ConntrackLocal, {len(ct_names)} maps)" if args.ct_local else ""),
-            "packets_per_step_per_gpu": int(batches[W].n),
+            "packets_per_step_per_gpu": int(n_of[W]),
             "address_pairs_per_gpu": int(args.pairs),
             "address_pairs": int(args.pairs) * world,
             "ct_max_entries": int(ct_max),
@@ -651,8 +747,35 @@ def ct_local_split(sc, P, ct_max):
     return names
 
 
-def oracle_config2(args, B, sc, st, dp, batches, ps, outs, W, K, world=1, local_world=1, L=None,
-                   ct_names=("cilium_ct4_global",)):
+STEP_BLOCK = 32          # config 2: steps resident in device memory at a time (~0.7 GB each)
+
+
+def parity_sample2(args, st, world, local_world, L):
+    """Config 2's parity sample, fixed before the steps run (each block keeps its
+    sampled packets): host threads, the divisor, the per-pair sample bit and the bit of
+    the 1/8 subsample that runs on one core first."""
+    import torch
+    from oracle import parity as PY
+    T = cpu_threads(local_world)
+    div = parity_div(args, world, T, L * 4 * args.flows_per_step)
+    if world == 1 and not args.parity_div:
+        div = max(1, -(-L // max(PARITY_WHOLE_STEPS, args.long_steps)))
+    sa, da = st.p_saddr.cpu().numpy(), st.p_daddr.cpu().numpy()
+    samp = torch.from_numpy(PY.pair_sampled(sa, da, div)).to(st.device)
+    one = torch.from_numpy(PY.pair_sampled(sa, da, div * 8)).to(st.device)
+    return {"T": T, "div": div, "samp": samp, "one": one}
+
+
+def parity_keep(ctx, cdict, p, out, with_one):
+    """(columns, records, single-core bits or None) of a step's sampled packets, on the device."""
+    import torch
+    if ctx["div"] == 1:
+        return cdict, out, ctx["one"][p] if with_one else None
+    idx = torch.nonzero(ctx["samp"][p]).squeeze(1)
+    return {k: v[idx] for k, v in cdict.items()}, out[idx], ctx["one"][p][idx] if with_one else None
+
+
+def oracle_config2(args, B, sc, dp, ctx, kept, W, K, world=1, L=None, ct_names=("cilium_ct4_global",)):
     """The CPU restatement (oracle, multi-threaded, RSS-style partition by flow
     group) over the flow-group sample of every step (warm-up included): its
     records must equal the GPU's for every sampled packet and, after the last
@@ -665,25 +788,19 @@ def oracle_config2(args, B, sc, st, dp, batches, ps, outs, W, K, world=1, local_
     from oracle.scenario import OracleDP
     from oracle import parity as PY
     L = L or W + K
-    T = cpu_threads(local_world)
-    div = parity_div(args, world, T, sum(b.n for b in batches[:L]))
+    T, div = ctx["T"], ctx["div"]
     t0 = time.time()
     ref = OracleDP(sc, shards=T)
     if div > 1:
         lru_replay(B, dp, ref)          # a sample cannot derive the whole table's cutoffs
-    sa, da = st.p_saddr.cpu().numpy(), st.p_daddr.cpu().numpy()
-    samp = torch.from_numpy(PY.pair_sampled(sa, da, div)).to(st.device)
-    one = torch.from_numpy(PY.pair_sampled(sa, da, div * 8)).to(st.device)
     par = Parity(f"1/{div} of the address pairs (whole flow groups), every step incl. warm-up")
     done = single_n = 0
     tt = single_t = 0.0
 
     def host_step(s):                                   # frames + GPU records of step s, on the host
-        idx = None if div == 1 else torch.nonzero(samp[ps[s]]).squeeze(1)
-        pk = cols_packets(batches[s].cdict, idx)
-        go = (outs[s] if idx is None else outs[s][idx]).cpu().numpy().view(ING_OUT).ravel()
-        m1 = (one[ps[s]] if idx is None else one[ps[s]][idx]).cpu().numpy() if s == W else None
-        return pk, go, m1
+        cd, go, m1 = kept.pop(s)
+        pk = cols_packets(cd, None)
+        return pk, go.cpu().numpy().view(ING_OUT).ravel(), None if m1 is None else m1.cpu().numpy()
     import concurrent.futures as cf
     prep = cf.ThreadPoolExecutor(1)                     # step s+1 is prepared while the oracle runs step s
     nxt = prep.submit(host_step, 0)
@@ -753,6 +870,8 @@ def oracle_config2(args, B, sc, st, dp, batches, ps, outs, W, K, world=1, local_
 # below that) and the wall time one rank's parity leg may take at N>1.
 ORACLE_MPPS_PER_THREAD = 0.4
 PARITY_LEG_S = 60.0
+PARITY_WHOLE_STEPS = 64   # N=1, config 2: up to this many steps every pair is compared; a longer run (a large
+                          # --steps) compares 1 pair in ceil(steps / 64), about as many packets as the 64-step leg
 
 
 def parity_div(args, world, threads=None, packets=None):
@@ -789,6 +908,7 @@ def bench_config1(args, B):
         lib.gf_xdp_classify(dp.xdp_prog, C.byref(c), out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     W, K = 5, 50
     el, c, _, kern = timed(B, step, W, K)
+    dump_outputs(args, "records", out)
     cpu = par = None
     if not args.no_cpu:
         from oracle.scenario import OracleDP
@@ -832,6 +952,7 @@ def bench_config3(args, B):
                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
     W, K = 3, 10
     el, c, _, kern = timed(B, step, W, K)
+    dump_outputs(args, "records", out)
     cpu = par = None
     if not args.no_cpu:
         from oracle.scenario import OracleDP
@@ -957,6 +1078,7 @@ def bench_config4(args, B, rank=0, world=1, ingest="owned", local_world=1):
                 fps[s] = PY.frame_fingerprints_torch(snap)
             got[s] = (fbs[s], samps[s], outs[s])
     el, c, lc, kern = timed(B, step, W, K, world)
+    dump_outputs(args, "records", got[W + K - 1][2])
     names = [k for k in kern]
     ranks = None
     if world > 1:
@@ -1170,6 +1292,7 @@ def bench_config5(args, B):
         got.append((fbs[-1], pm[p], torch.empty((f.shape[0], 24), dtype=torch.uint8, device=B.dev)))
     B.sync()
     el, c, _, kern = timed(B, lambda s: dp.pipeline(fbs[s], sc.now + s, out=got[s][2], snap_out=False), W, K)
+    dump_outputs(args, "records", got[W + K - 1][2])
     names = [k for k in kern]
     cpu = par = None
     if not args.no_cpu:
@@ -1223,6 +1346,7 @@ def bench_egress(args, B):
     fbs = [FrameBatch(frames[i], len_t, None, B.dev, lid_t, fh_t) for i in range(W + K)]
     outs = [torch.empty((n, 24), dtype=torch.uint8, device=B.dev) for _ in range(W + K)]
     el, c, _, kern = timed(B, lambda s: dp.egress(fbs[s], sc.now + s, out=outs[s], snap_out=False), W, K)
+    dump_outputs(args, "records", outs[W + K - 1])
     log(f"egress: timed {K} steps ({time.time() - t0:.1f}s)")
     cpu = par = None
     if not args.no_cpu:
@@ -1320,6 +1444,7 @@ def oracle_egress(args, B, sc, meta, dp, frames, lens, lid, fh, outs, W, K, ct_n
     return cpu, res
 
 
+EXTRA_MAX_STEPS = 20
 EXTRA = {"1": bench_config1, "3": bench_config3, "4": bench_config4, "5": bench_config5, "egress": bench_egress}
 
 
@@ -1474,8 +1599,18 @@ def spawn_ranks(n, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
-    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=8,
+                    help="timed steps of config 2 (the headline), any number; --config 4 and egress time "
+                         "max(4, steps / 2) steps, configs 1, 3 and 5 a fixed number.  --full with more than "
+                         "64 steps in all compares a pair sample and replays the device's eviction log "
+                         "instead of checking it against the oracle's own cutoffs")
+    ap.add_argument("--warmup", type=int, default=4, help="untimed steps before them (config 2: at least 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines and parity legs, "
+                         "config 2's long-horizon continuation, the other configurations, config 4's H2D leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step to DIR/records.npy (float32, one column per "
+                         "record byte; a fixed seeded row sample when they exceed 48 MB, rows in records_rows.npy)")
     ap.add_argument("--config", default="2", choices=["1", "2", "3", "4", "5", "egress"],
                     help="BASELINE configuration printed as the line (default: 2, the headline)")
     ap.add_argument("--flows-per-step", type=int, default=4 << 20)
@@ -1484,14 +1619,15 @@ def main():
                     help="CT max_entries (LRU): 134,217,728, above the entries a default run creates")
     ap.add_argument("--ct6-prefill", type=int, default=8_000_000)
     ap.add_argument("--long-steps", type=int, default=64,
-                    help="config 2 at N=1: steps in all (warm-up + timed + a timed continuation into LRU eviction)")
+                    help="config 2 at N=1: steps in all (warm-up + timed + a timed continuation into LRU eviction, "
+                         "which only --full runs)")
     ap.add_argument("--ct6-max", type=int, default=10_485_760, help="config 5: CT6 max_entries (LRU)")
     ap.add_argument("--c5-flows", type=int, default=1 << 20, help="config 5: new flows per step")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the parity legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and the parity legs")
     ap.add_argument("--pipeline", action="store_true",
                     help="config 2: the steps through gf_policy_ingress_classify_batches (schedule overlap)")
-    ap.add_argument("--no-extra", action="store_true", help="config 2 only (skip the other configurations)")
-    ap.add_argument("--no-h2d", action="store_true", help="config 4: skip the leg with the host->device copy")
+    ap.add_argument("--no-extra", action="store_true", help="--full with config 2 only (skip the other configurations)")
+    ap.add_argument("--no-h2d", action="store_true", help="--full, config 4: skip the leg with the host->device copy")
     ap.add_argument("--ct-local", action="store_true",
                     help="configs 2 and egress: every endpoint on CT maps of its own (the ConntrackLocal option)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -1503,6 +1639,9 @@ def main():
     ap.add_argument("--c4-frames", default="warmup", choices=["none", "warmup", "all"],
                     help="config 4: steps whose rewritten frames are fingerprinted and compared with the oracle's")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the configuration's own timed steps and nothing beside them
+        args.no_cpu = args.no_extra = args.no_h2d = True
 
     rehearsal = bool(os.environ.get("GPUFLOW_BENCH_SELFTEST"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1534,6 +1673,10 @@ def main():
             {"4": lambda a, b: bench_config4(a, b, rank, world, "owned", local_world)})
         if extra:
             res["configs"] = {}
+            args.dump_outputs = None                     # the dump is the line's configuration's alone
+            # --steps sizes the headline; the other configurations keep every step's frames and
+            # compare every packet, so beside it they run at most the steps of --steps 20
+            args.steps = min(args.steps, EXTRA_MAX_STEPS)
         for k, fn in extra.items():
             t0 = time.time()
             try:

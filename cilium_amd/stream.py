@@ -39,6 +39,24 @@ def _h(torch, x, k):
     return (x ^ (x >> 31)) & 0x7FFFFFFFFFFFFFFF
 
 
+def _last_occurrence(torch, *cols):
+    """Ascending indices of the last occurrence of each distinct row of the int64
+    columns `cols` (what synth.dedup keeps, in the order it keeps it)."""
+    n = len(cols[0])
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=cols[0].device)
+    perm = torch.arange(n, device=cols[0].device)
+    for c in reversed(cols):                                 # stable passes, least significant column first
+        perm = perm[torch.sort(c[perm], stable=True).indices]
+    last = torch.ones(n, dtype=torch.bool, device=perm.device)
+    same = torch.ones(n - 1, dtype=torch.bool, device=perm.device)
+    for c in cols:
+        s = c[perm]
+        same &= s[1:] == s[:-1]
+    last[:-1] = ~same                                        # equal rows keep their order: the group's last is its latest
+    return torch.sort(perm[last]).values
+
+
 def pair_rank(raddr, ep_ip, world):
     a, b = np.minimum(raddr, ep_ip).astype(np.uint64), np.maximum(raddr, ep_ip).astype(np.uint64)
     return (synth.mix32((b << np.uint64(32)) | a) % np.uint32(world)).astype(np.int64)
@@ -91,19 +109,36 @@ class Stream:
     def reply_ct_entries(self, n_steps):
         """Egress-created CT entries (tuple + ICMP related) for every reply flow
         of steps [0, n_steps): keys/values in ipv4_ct_tuple / ct_entry layout."""
+        # Built on the stream's device, a block of steps at a time, so that a long run's
+        # set-up stays short: the rows are synth.ct4_keys(E, R, raw16(sport), raw16(dport),
+        # proto, 0) followed by the related keys ct4_keys(E, R, 0, 0, ICMP, 2), every key
+        # kept once at its last occurrence (synth.dedup), every value the same ct_vals row.
         torch = self.torch
-        f = torch.arange(0, n_steps * self.F, device=self.device, dtype=torch.int64)
-        p, proto, sport, dport, reply, related, rst = self._flows(f)
-        m = reply & (proto != ICMP)
-        p, proto, sport, dport = p[m], proto[m], sport[m], dport[m]
-        E, R = self.p_daddr[p].cpu().numpy(), self.p_saddr[p].cpu().numpy()
-        E, R = _bswap32(E), _bswap32(R)                      # host order for synth helpers
-        sp, dp, pr = sport.cpu().numpy(), dport.cpu().numpy(), proto.cpu().numpy()
-        n = len(E)
-        k = synth.ct4_keys(E, R, synth.raw16(sp), synth.raw16(dp), pr, np.zeros(n))
-        rk = synth.ct4_keys(E, R, np.zeros(n), np.zeros(n), np.full(n, ICMP), np.full(n, 2))
-        v = synth.ct_vals(n, 100_000 + 43200, 16, 0, 0, tx=(1, 100))
-        return synth.dedup(np.concatenate([k, rk]), np.concatenate([v, v]))
+        total, block = n_steps * self.F, 16 * self.F
+        ps, ws = [], []
+        for a in range(0, total, block):
+            f = torch.arange(a, min(a + block, total), device=self.device, dtype=torch.int64)
+            p, proto, sport, dport, reply, related, rst = self._flows(f)
+            m = reply & (proto != ICMP)
+            ps.append(p[m])
+            ws.append((sport[m] << 24) | (dport[m] << 8) | proto[m])
+        p, w = torch.cat(ps), torch.cat(ws)
+        del ps, ws
+        addr = (self.p_daddr[p] << 32) | self.p_saddr[p]     # the key's two addresses as one word
+        ik = _last_occurrence(torch, addr, w)
+        ir = _last_occurrence(torch, addr)
+        u8 = lambda x, sh: ((x >> sh) & 0xff).to(torch.uint8)
+
+        def rows(i, related_key):
+            d, s, x = self.p_daddr[p[i]], self.p_saddr[p[i]], w[i]
+            z = torch.zeros(len(i), dtype=torch.uint8, device=self.device)
+            l4 = [z, z, z, z, z + ICMP, z + 2] if related_key else \
+                 [u8(x, 32), u8(x, 24), u8(x, 16), u8(x, 8), u8(x, 0), z]
+            return torch.stack([u8(d, 0), u8(d, 8), u8(d, 16), u8(d, 24), u8(s, 0), u8(s, 8), u8(s, 16), u8(s, 24)]
+                               + l4, dim=1)
+        k = torch.cat([rows(ik, False), rows(ir, True)]).cpu().numpy()
+        v = synth.ct_vals(1, 100_000 + 43200, 16, 0, 0, tx=(1, 100))
+        return k, np.repeat(v, len(k), axis=0)
 
     # ---- one step -----------------------------------------------------------
     def step(self, s):

@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--pairs", "512", "--flows-per-step", "2048", "--steps", "2", "--warmup", "1", "--ct-max", "65536"]
+SMALL = ["--full", "--pairs", "512", "--flows-per-step", "2048", "--steps", "2", "--warmup", "1", "--ct-max", "65536"]
 
 # The parent runs bench.py's main() in-process and reports whether it imported
 # torch (i.e. could have initialised the HIP runtime) before the ranks ended.
@@ -134,7 +134,7 @@ def test_egress_sharded_parity_equals_sequential():
     env = dict(os.environ, GPUFLOW_BENCH_SELFTEST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "egress", "--egress-flows", "65536",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "egress", "--egress-flows", "65536",
                         "--steps", "8"], env=env, capture_output=True, text=True, timeout=600, cwd="/tmp")
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     par = r["parity"]
@@ -151,7 +151,7 @@ def test_config5_independent_eviction_rehearsal():
     env = dict(os.environ, GPUFLOW_BENCH_SELFTEST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5", "--pairs", "4096",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "5", "--pairs", "4096",
                         "--ct6-prefill", "30000", "--ct6-max", "32768", "--c5-flows", "8192"],
                        env=env, capture_output=True, text=True, timeout=600, cwd="/tmp")
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -168,7 +168,7 @@ def test_config2_ct_local_rehearsal():
     env = dict(os.environ, GPUFLOW_BENCH_SELFTEST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ct-local", "--no-extra", "--pairs", "4096",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--ct-local", "--no-extra", "--pairs", "4096",
                         "--flows-per-step", "16384", "--steps", "4", "--warmup", "3", "--long-steps", "12",
                         "--ct-max", "65536"], env=env, capture_output=True, text=True, timeout=600, cwd="/tmp")
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -187,7 +187,7 @@ def test_egress_ct_local_sharded_parity_rehearsal():
     env = dict(os.environ, GPUFLOW_BENCH_SELFTEST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "egress", "--ct-local",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "egress", "--ct-local",
                         "--egress-flows", "65536", "--steps", "8"], env=env, capture_output=True, text=True,
                        timeout=600, cwd="/tmp")
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -195,3 +195,131 @@ def test_egress_ct_local_sharded_parity_rehearsal():
     (name, t), = par["tables"].items()
     assert name == "256 per-endpoint maps" and t["mismatches"] == 0 and t["entries_compared"] > 100_000, par
     assert par["mismatches"] == 0 and par["packets_compared"] == 65536 * par["steps"]
+
+
+def _plain(tmp, extra=(), steps="5"):
+    env = dict(os.environ, GPUFLOW_BENCH_SELFTEST="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pairs", "512",
+                        "--flows-per-step", "2048", "--steps", steps, "--warmup", "3", "--ct-max", "65536",
+                        "--dump-outputs", str(tmp)] + list(extra), env=env, capture_output=True, text=True,
+                       timeout=600, cwd=str(tmp))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return lines[0]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps of the headline configuration
+    and runs nothing beside them: no CPU baseline, no parity leg, no continuation, no
+    other configuration.  --dump-outputs writes the last timed step's records as
+    float32, identical from run to run; --full computes the same records (rehearsed)."""
+    import numpy as np
+    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    for d in (a, b, c):
+        d.mkdir()
+    r = _plain(a)
+    assert r["steps"] == 5 and r["warmup"] == 3 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "Mpps" and r["higher_is_better"] is True and r["dtype"] == "u32"
+    assert r["cpu_baseline"] is None and r["parity"] is None and r["long_horizon"] is None and "configs" not in r
+    v = r["verdicts"]
+    assert v["pass"] + v["drop"] + v["redirect"] == 5 * r["config"]["packets_per_step_per_gpu"]
+    ra = np.load(a / "records.npy")
+    assert ra.dtype == np.float32 and ra.shape == (r["config"]["packets_per_step_per_gpu"], 8)
+    assert ra.min() >= 0 and ra.max() <= 255 and ra.any()
+    _plain(b)
+    assert np.array_equal(ra, np.load(b / "records.npy"))
+    f = _plain(c, ["--full"])
+    assert f["parity"]["mismatches"] == 0 and f["steps"] == 5 and f["configs"]["4"]["parity"]["mismatches"] == 0
+    assert np.array_equal(ra, np.load(c / "records.npy"))
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path, monkeypatch):
+    """Records beyond the dump's byte budget: a fixed, ascending row sample, the
+    same rows every time, with the row numbers beside the records."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40 * 100)
+    monkeypatch.delenv("RANK", raising=False)
+    t = (torch.arange(1000 * 8, dtype=torch.int64) % 251).to(torch.uint8).reshape(1000, 8)
+    for d in ("x", "y"):
+        bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / d)), "records", t)
+    rows, rec = np.load(tmp_path / "x" / "records_rows.npy"), np.load(tmp_path / "x" / "records.npy")
+    assert rows.dtype == np.float64 and rec.dtype == np.float32 and rec.shape == (100, 8)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 1000
+    assert np.array_equal(rec, t.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(rows, np.load(tmp_path / "y" / "records_rows.npy"))
+    assert np.array_equal(rec, np.load(tmp_path / "y" / "records.npy"))
+    bench.dump_outputs(types.SimpleNamespace(dump_outputs=None), "records", t)      # off: writes nothing
+
+
+def test_long_run_holds_one_block_and_samples_its_parity(tmp_path):
+    """--steps beyond one resident block (bench.STEP_BLOCK) and beyond the 64 steps whose
+    parity is whole: the plain run times every step block by block, --full compares a
+    pair sample (whole flow groups, evictions replayed) and returns the same records."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 70 > 2 * bench.STEP_BLOCK and 73 > bench.PARITY_WHOLE_STEPS
+    a, b = tmp_path / "a", tmp_path / "b"
+    a.mkdir(), b.mkdir()
+    r = _plain(a, steps="70")
+    v = r["verdicts"]
+    assert r["steps"] == 70 and v["pass"] + v["drop"] + v["redirect"] == 70 * r["config"]["packets_per_step_per_gpu"]
+    f = _plain(b, ["--full", "--no-extra"], steps="70")
+    par = f["parity"]
+    assert par["sample"].startswith("1/2 of the address pairs") and par["steps"] == 73
+    assert par["mismatches"] == 0 and par["ct_mismatches"] == 0 and par["packets_compared"] > 73 * 2048
+    assert f["verdicts"] == v and np.array_equal(np.load(a / "records.npy"), np.load(b / "records.npy"))
+
+
+def test_reply_ct_entries_equal_the_host_construction():
+    """Stream.reply_ct_entries builds the pre-inserted CT rows on the stream's device;
+    they are the rows synth.ct4_keys / ct_vals / dedup give on the host, in the same order
+    (few pairs: many repeated keys)."""
+    import numpy as np
+    import torch
+    from cilium_amd import synth, stream
+    from cilium_amd.stream import ICMP, _bswap32
+    for pairs, F, steps in ((64, 4096, 7), (2048, 1 << 14, 20)):
+        sc, P, _ = synth.config2_tables(n_pairs=pairs, ct_max=65536, n_ep=16, n_ids=256, n_l3=64, n_l4=128, n_wc=8,
+                                        n_cidr=16)
+        st = stream.Stream(P, flows_per_step=F, device="cpu")
+        p, proto, sport, dport, reply, related, rst = st._flows(torch.arange(0, steps * F, dtype=torch.int64))
+        m = reply & (proto != ICMP)
+        E, R = _bswap32(st.p_daddr[p[m]].numpy()), _bswap32(st.p_saddr[p[m]].numpy())
+        n = len(E)
+        k = synth.ct4_keys(E, R, synth.raw16(sport[m].numpy()), synth.raw16(dport[m].numpy()), proto[m].numpy(),
+                           np.zeros(n))
+        rk = synth.ct4_keys(E, R, np.zeros(n), np.zeros(n), np.full(n, ICMP), np.full(n, 2))
+        val = synth.ct_vals(n, 100_000 + 43200, 16, 0, 0, tx=(1, 100))
+        wk, wv = synth.dedup(np.concatenate([k, rk]), np.concatenate([val, val]))
+        gk, gv = st.reply_ct_entries(steps)
+        assert len(wk) < 2 * n and gk.dtype == np.uint8 and gv.dtype == np.uint8
+        assert np.array_equal(gk, wk) and np.array_equal(gv, wv)
+
+
+def test_n8_projection_reads_a_full_run(tmp_path):
+    """tools/n8_projection.py projects the 8-rank run from the stderr log and the JSON
+    line of an N=1 `bench.py --full` run: the log still carries every line it parses
+    (tables, generated N steps, cpu baseline + parity, config 4), rehearsed here."""
+    parent, lines, err = _run(1)
+    assert parent["rc"] == 0, err[-3000:]
+    (tmp_path / "run.log").write_text(err)
+    (tmp_path / "run.json").write_text(json.dumps(lines[0]) + "\n")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "n8_projection.py"), str(tmp_path / "run.log"),
+                        str(tmp_path / "run.json")], capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(p.stdout)
+    n1 = out["n1"]
+    W, K = lines[0]["warmup"], lines[0]["steps"]
+    assert n1["stream_steps"] == max(64, W + K) and n1["stream_s"] >= n1["tables_s"] >= 0
+    assert n1["parity_packets"] == lines[0]["parity"]["packets_compared"] and n1["config4_s"] is not None
+    assert set(out["projection"]) == {"T2", "T4", "T16"}
+    for v in out["projection"].values():
+        assert v["config2_s"] > 0 and v["config2_parity_div"] >= 2 and v["total_s"] > 0

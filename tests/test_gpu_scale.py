@@ -211,3 +211,15 @@ def test_config4_real_shape_sampled():
     ok, ov = PY.oracle_table_sampled(ref.m["cilium_ct4_global"], div)
     n, bad = PY.compare_tables(gk, gv, ok, ov)
     assert bad == 0 and n > 100_000, (n, bad, gtot)
+
+
+def test_reply_ct_entries_on_the_device_equal_the_cpu_build():
+    """Stream.reply_ct_entries sorts and de-duplicates on the stream's device: on the
+    GPU it must give the rows the CPU device gives (which tests/test_bench_launcher.py
+    pins to the host construction), in the same order; few pairs, so most keys repeat,
+    and more than one 16-step block."""
+    sc, P, _ = synth.config2_tables(n_pairs=256, ct_max=65536, n_ep=16, n_ids=256, n_l3=64, n_l4=128, n_wc=8,
+                                    n_cidr=16)
+    gk, gv = stream.Stream(P, flows_per_step=1 << 14, device="cuda").reply_ct_entries(21)
+    ck, cv = stream.Stream(P, flows_per_step=1 << 14, device="cpu").reply_ct_entries(21)
+    assert len(ck) > 10_000 and np.array_equal(gk, ck) and np.array_equal(gv, cv)

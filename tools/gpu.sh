@@ -11,7 +11,8 @@
 #
 #   tests[:EXPR]            pytest -m gpu [-k EXPR] ('+' for spaces)     -> tests.txt
 #   smoke                   __graft_entry__.smoke()                      -> smoke.txt
-#   bench:NAME[:ARGS]       python bench.py ARGS                         -> NAME.json, NAME.err
+#   bench:NAME[:ARGS]       python bench.py ARGS (ARGS --full: the whole line, with the CPU baselines,
+#                           parity and the other configurations)         -> NAME.json, NAME.err
 #   vbench:VAR:NAME[:ARGS]  bench.py on the variant library VAR (tools/variant.sh build VAR ...):
 #                           a variant whose sources are not this tree's is rebuilt here first,
 #                           from the flags it was built with (tools/_bin/libgpuflow_VAR.flags)

@@ -1,5 +1,5 @@
-"""Wall-time projection of the driver's `bench.py --gpus 8` run from an N=1 run's
-own phase times (its stderr log and JSON line) — the scaling run's per-rank work is
+"""Wall-time projection of the driver's `bench.py --gpus 8` run from the phase times
+of an N=1 `bench.py --full` run (its stderr log and JSON line) — the scaling run's per-rank work is
 the N=1 work with L = W + K steps and no long horizon, and its parity sample is
 bench.parity_div's (sized to the rank's share of the host's cores).
 
@@ -37,7 +37,7 @@ def main():
     t_gen = float(re.search(r"generated (\d+) steps \(([\d.]+)s\)", log).group(2))
     steps_gen = int(re.search(r"generated (\d+) steps", log).group(1))
     m = re.search(r"cpu baseline \+ parity: (\d+) packets compared.*on (\d+) threads \(([\d.]+)s\)", log)
-    par_pk, par_thr, par_s = int(m.group(1)), int(m.group(2)), float(m.group(3)) - t_gen
+    par_pk, par_thr, par_s = int(m.group(1)), int(m.group(2)), max(float(m.group(3)) - t_gen, 1e-3)
     rate_thread = par_pk / par_s / par_thr               # packets / s / thread, compare included
     c4 = (r.get("configs") or {}).get("4") or {}
     m4 = re.search(r"config 4: [\d.]+ Mpps \(([\d.]+)s\)", log)
