@@ -30,6 +30,7 @@ lib = C.CDLL(LIB_PATH)
 
 GF_MAX_L4_INGRESS = 64
 GF_STATS_WORDS = 512
+GF_LXC_F_NO_CONNTRACK = 1 << 7   # the endpoint's Conntrack option disabled; ct_map4 / ct_map6 may then be 0
 
 
 class gf_map_info(C.Structure):

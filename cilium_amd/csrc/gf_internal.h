@@ -237,6 +237,7 @@ struct PolicyArray : Obj {
     std::vector<uint8_t> h_cfgs;       // last uploaded program table (change detection)
     std::vector<uint16_t> h_slot_of;
     bool dirty = true;
+    int noct = 0;              // programs with GF_LXC_F_NO_CONNTRACK: 0 none, 1 some, 2 every one (gf_policy_array_update)
     std::mutex mu;             // one classify call at a time per array (its device image)
     OrderPt ord;
     PolicyArray() : Obj(ObjKind::PolicyArray) {}

@@ -2085,6 +2085,167 @@ __global__ __launch_bounds__(BLOCK, FAM == 6 ? GF_ING_MINW6 : GF_ING_MINW) void 
     if (stats) st.flush(stats);
 }
 
+// ---- programs without conntrack (GF_LXC_F_NO_CONNTRACK: CONNTRACK undefined) ----
+// bpf/lib/conntrack.h:582-617: ct_lookup4/6 return 0 (CT_NEW) and touch neither a
+// map nor the tuple, ct_create4/6 return 0, ct_delete4/6 are empty.  What is left of
+// ipv4_policy / ipv6_policy (bpf_lxc.c:865-970, 745-862): the tuple keeps the frame's
+// addresses unreversed and ports / flags 0, no L4 header byte is read, the policy is
+// asked with dport 0 and every packet a rule does not allow is DROP_POLICY (nothing
+// is a reply or related).  A packet reads no CT line and is ordered against no
+// other packet, so these packets take no part in the flow-group schedule: one thread
+// per packet in batch order (k_ing_noct).
+// policy_can_access_ingress with the counter update, the entry counted at once
+// (policy.h:67-92; counter sums commute).
+__device__ __forceinline__ int policy_ingress_noct(const IngCtx &X, const Ep &ep, uint32_t identity, uint32_t proto,
+                                                   uint32_t len, bool v6, const uint32_t *cidr_addr, uint32_t &ab) {
+    PolLine pl;
+    int64_t fc;
+    const int v = policy_lookup(X, ep, pl, false, identity, 0u, proto, v6, cidr_addr, ab, fc);
+    if (fc >= 0) pol_count_add(ep.pol_side + (uint64_t)fc * GF_POL_SIDE, 1u, len, false);
+    return v;
+}
+// ipv{4,6}_redirect_to_host_port of a verdict > 0 (ret == CT_NEW always holds): the
+// proxy-map key and the port rewrite come from the unfilled tuple (sport and the old
+// dport 0, key .saddr = the frame's daddr)
+__device__ __forceinline__ int redirect_noct(const IngCtx &X, const gf_rec &r, uint32_t i, int verdict, V6Tuple tv,
+                                             bool v6, uint4 od, uint8_t &ofl, uint16_t &proxy, uint32_t &ifindex) {
+    if (X.tmark)
+        trace_proxy(X.tmark, X.tcap, X.snap ? X.snap + (size_t)i * X.snap_stride : nullptr, nullptr, 0,
+                    trace_cap_len(r.len, X.snap_stride), i, GF_TR_PX_POLICY);
+    const int r3 = redirect_checks(r.len, r.l4_off, r.proto);
+    if (r3 < 0) return r3;
+    if (X.snap || X.plog) {
+        if (v6) pol_redirect_ol(pol_ctx(X), i, r.len, r.l4_off, r.proto, tv, (uint32_t)verdict & 0xffffu, od, r.src_identity);
+        else { const uint32_t odw[1] = {od.x}; pol_redirect(X, i, r.len, r.l4_off, r.proto, tv.w, false, (uint32_t)verdict & 0xffffu, odw, r.src_identity); }
+    }
+    ifindex = X.host_ifindex;
+    ofl |= GF_INGRESS_F_PROXY;
+    proxy = (uint16_t)verdict;
+    return 0;
+}
+// handle_policy (bpf_lxc.c:980-1024) of a program without conntrack
+__device__ __forceinline__ gf_ingress_out handle_policy_noct(const IngCtx &X, const gf_rec &r, uint32_t i, uint32_t &ab) {
+    gf_ingress_out o{};
+    if (!r.ep) { o.action = TC_SHOT; o.reason = 140; return o; }   // missed tail call (DROP_MISSED_TAIL_CALL)
+    Ep ep;
+    ep.init();
+    ep.use(X, r.ep);
+    const uint32_t flags = ep.flags, len = r.len, nh = r.proto, cls = r.cls & 3u;
+    int ret;
+    uint8_t fl = 0;
+    uint16_t proxy = 0;
+    uint32_t ifindex = r.ifindex;
+    if (flags & GF_LXC_F_DROP_ALL) ret = D_POLICY;
+    else if (cls == 2) {                                // ipv6_policy
+        ab += 47;
+        if (len < 54 || !X.daddr6 || !X.saddr6) ret = D_INVALID;
+        else {
+            const uint4 d = gload<uint4>(X.daddr6 + (size_t)X.a6_stride * i);
+            const uint4 s = gload<uint4>(X.saddr6 + (size_t)X.a6_stride * i);
+            const uint32_t co = csum_l4_offset(nh), rn_new = d.w & 0xffffu;   // the rev-NAT index in the address (:776-790)
+            ret = 0;
+            if (rn_new) {
+                if (X.snap) pol_v6_zero_rn_ol(pol_ctx(X), i, len, r.l4_off, nh, rn_new);
+                if (co && !l4csum_ok(r.l4_off + (int)co, len)) ret = D_CSUM_L4;
+            }
+            if (!ret) {
+                const uint32_t sa[4] = {s.x, s.y, s.z, s.w};
+                int verdict = policy_ingress_noct(X, ep, r.src_identity, nh, len, true, sa, ab);
+                if (verdict < 0) ret = D_POLICY;
+                else {
+                    if (r.cls & 4) verdict = 0;         // skip_proxy
+                    if (verdict > 0) {
+                        V6Tuple tv{{d.x, d.y, d.z, d.w, s.x, s.y, s.z, s.w, 0u, nh}};
+                        ret = redirect_noct(X, r, i, verdict, tv, true, d, fl, proxy, ifindex);
+                    }
+                }
+            }
+        }
+    }
+    else if (cls == 1 && (flags & GF_LXC_F_LXC_IPV4)) { // ipv4_policy
+        ab += 23;
+        if (len < 34) ret = D_INVALID;
+        else {
+            const uint32_t sa[1] = {r.saddr};
+            int verdict = policy_ingress_noct(X, ep, r.src_identity, nh, len, false, sa, ab);
+            ret = 0;
+            if (verdict < 0) ret = D_POLICY;
+            else {
+                if (r.cls & 4) verdict = 0;
+                if (verdict > 0) {
+                    V6Tuple tv{{r.daddr, r.saddr, 0u, nh, 0u, 0u, 0u, 0u, 0u, 0u}};
+                    ret = redirect_noct(X, r, i, verdict, tv, false, make_uint4(r.daddr, 0u, 0u, 0u), fl, proxy, ifindex);
+                }
+            }
+        }
+    }
+    else ret = D_UNKNOWN_L3;
+    if (ret < 0) { o.action = TC_SHOT; o.reason = (uint8_t)(-ret); return o; }
+    o.flags = fl;
+    o.proxy_port = proxy;
+    o.ifindex_lo = (uint16_t)ifindex;
+    o.action = ifindex ? TC_REDIRECT : TC_OK;
+    return o;
+}
+// A mixed array: the packets of programs without conntrack leave the flow-group
+// sort's live range (the grouped kernels never see them).
+__global__ __launch_bounds__(BLOCK) void k_ing_noct_mark(uint32_t n, const gf_rec *rec, const gf_lxc_dev *cfgs,
+                                                         uint32_t *keys) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t ep = rec[i].ep;
+    if (ep && (cfgs[ep - 1].flags & GF_LXC_F_NO_CONNTRACK)) keys[i] = GF_KEY_SKIP;
+}
+// One thread per packet in batch order: coalesced record reads and out[i] (or pipeline
+// record, X.pout) writes, the
+// block's counter bins in LDS, policy counters by atomics, no lane state.
+// all: every program of the array is without conntrack (the kernel then also reports
+// the packets of empty slots); else it runs exactly the packets k_ing_noct_mark took
+// out of the schedule.
+__global__ __launch_bounds__(BLOCK) void k_ing_noct(IngCtx X, uint32_t n, uint32_t all, const gf_rec *rec,
+                                                    gf_ingress_out *out, unsigned long long *stats) {
+    __shared__ uint32_t sl[272];
+    Stats st{sl};
+    if (stats) st.init();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool act = false;
+    gf_ingress_out o{};
+    uint32_t len = 0, ab = 0;
+    if (i < n) {
+        const gf_rec r = rec[i];
+        act = !(r.cls & 8) && (all || (r.ep && (gload<uint32_t>(&X.cfgs[r.ep - 1].flags) & GF_LXC_F_NO_CONNTRACK)));
+        if (act) {
+            len = r.len; ab = 8;                        // output record
+            o = handle_policy_noct(X, r, i, ab);
+            if (X.pout && X.pout_wo) {                  // complete the pipeline record: stores only (as ing_one)
+                uint8_t *q = X.pout + 24 * (size_t)i;
+                const uint32_t ff = ((uint32_t)(r.cls >> 4) & 7u) << 5;   // the front's whole GF_PIPE_F_* byte
+                *reinterpret_cast<uint32_t *>(q) = GF_STAGE_POLICY | ((uint32_t)o.action << 8) | ((uint32_t)o.reason << 16) |
+                                                   ((uint32_t)o.ct_ret << 24);
+                *reinterpret_cast<uint32_t *>(q + 4) = (ff | o.flags) | ((uint32_t)o.proxy_port << 16);
+                *reinterpret_cast<uint16_t *>(q + 8) = o.ifindex_lo;
+            } else if (X.pout) {                        // a record whose other bytes are kept
+                uint8_t *q = X.pout + 24 * (size_t)i;
+                uint2 a = *reinterpret_cast<const uint2 *>(q);
+                uint2 b = *reinterpret_cast<const uint2 *>(q + 8);
+                a.x = (a.x & 0xffu) | ((uint32_t)o.action << 8) | ((uint32_t)o.reason << 16) | ((uint32_t)o.ct_ret << 24);
+                a.y = ((a.y & 0xffu) | o.flags) | (a.y & 0xff00u) | ((uint32_t)o.proxy_port << 16);
+                b.x = (b.x & 0xffff0000u) | o.ifindex_lo;
+                *reinterpret_cast<uint2 *>(q) = a;
+                *reinterpret_cast<uint2 *>(q + 8) = b;
+            } else {
+                out[i] = o;
+            }
+        }
+    }
+    if (stats) {                                        // (every lane: wave sums; all CT_NEW)
+        st.pkt_wave(act, o.reason, o.action, len, ab);
+        const uint32_t c = (uint32_t)__popcll(__ballot(act));
+        if ((threadIdx.x & 63u) == 0) st.add_n(264, c);
+        st.flush(stats);
+    }
+}
+
 #define GF_LCAP 1024u
 // Bucket-size histogram per family (bit 31 of the bucket's sorted key):
 // block-local LDS bins, one global add per non-empty bin.
@@ -5340,12 +5501,17 @@ int gf_lxc_prog_load(const gf_lxc_cfg *cfg) {
     if (cfg->n_l4_ingress > GF_MAX_L4_INGRESS || cfg->n_l4_egress > GF_MAX_L4_INGRESS ||
         cfg->n_portmap > GF_MAX_PORTMAP)
         return -E2BIG;
+    // CONNTRACK undefined: CFG_L3L4_* is refused (bpf/lib/l4.h:138-139); the CT maps and
+    // CONNTRACK_ACCOUNTING mean nothing to the stub ct_* (conntrack.h:582-617)
+    const bool noct = (cfg->flags & GF_LXC_F_NO_CONNTRACK) != 0;
+    if (noct && (cfg->n_l4_ingress || cfg->n_l4_egress)) return -EINVAL;
     auto p = std::make_shared<ProgLxc>();
     p->cfg = *cfg;
+    if (noct) { p->cfg.ct_map4 = p->cfg.ct_map6 = 0; p->cfg.flags &= ~GF_LXC_F_CT_ACCOUNTING; }
     struct B { int h; uint32_t k, v; bool lpm; std::shared_ptr<Map> *out; };
     B binds[] = {
-        {cfg->policy_map, 8, 24, false, &p->policy}, {cfg->ct_map4, 14, 48, false, &p->ct4},
-        {cfg->ct_map6, 40, 48, false, &p->ct6},      {cfg->cidr4_ingress_map, 8, 0, true, &p->cidr4},
+        {cfg->policy_map, 8, 24, false, &p->policy}, {p->cfg.ct_map4, 14, 48, false, &p->ct4},
+        {p->cfg.ct_map6, 40, 48, false, &p->ct6},      {cfg->cidr4_ingress_map, 8, 0, true, &p->cidr4},
         {cfg->cidr6_ingress_map, 20, 0, true, &p->cidr6}, {cfg->revnat4_map, 2, 6, false, &p->revnat4},
         {cfg->revnat6_map, 2, 18, false, &p->revnat6},
         {cfg->lb4_services, 8, 12, false, &p->lb4},      {cfg->ipcache_map, 20, 8, false, &p->ipcache},
@@ -5411,11 +5577,18 @@ int gf_policy_array_update(int array, uint32_t lxc_id, int prog) {
     if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
     if (lxc_id > 0xffff) return -E2BIG;
     auto a = std::static_pointer_cast<PolicyArray>(o);
-    if (!prog) { a->slots.erase(lxc_id); a->dirty = true; return 0; }
-    auto po = get_obj(prog);
-    if (!po || po->kind != ObjKind::ProgLxc) return -EINVAL;
-    a->slots[lxc_id] = std::static_pointer_cast<ProgLxc>(po);
+    if (prog) {
+        auto po = get_obj(prog);
+        if (!po || po->kind != ObjKind::ProgLxc) return -EINVAL;
+        a->slots[lxc_id] = std::static_pointer_cast<ProgLxc>(po);
+    } else {
+        a->slots.erase(lxc_id);
+    }
     a->dirty = true;
+    size_t off = 0;                                     // programs without conntrack: none, some, every one
+    for (auto &kv : a->slots)
+        if (kv.second->cfg.flags & GF_LXC_F_NO_CONNTRACK) off++;
+    a->noct = !off ? 0 : off == a->slots.size() ? 2 : 1;
     return 0;
 }
 
@@ -5443,6 +5616,10 @@ static bool array_traces(const std::shared_ptr<PolicyArray> &a) {
         if (kv.second->cfg.flags & GF_LXC_F_TRACE_NOTIFY) return true;
     return false;
 }
+// Programs without conntrack (GF_LXC_F_NO_CONNTRACK) in an array: 0 none, 1 some, 2 every one.
+// Kept on the array by gf_policy_array_update (a program's flags never change).
+static int array_noct(const std::shared_ptr<PolicyArray> &a) { return a->noct; }
+
 static int trace_prepare(uint32_t n, bool with_in, hipStream_t s) {
     TraceWs &t = trace_ws();
     auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
@@ -6162,6 +6339,15 @@ static int lru_evict_maps(const std::vector<std::shared_ptr<Map>> &ms, uint32_t 
     return 0;
 }
 
+// A mixed array's packets of programs without conntrack out of the schedule (ws().keys).
+static int noct_mark(const std::shared_ptr<PolicyArray> &a, uint32_t n, hipStream_t s) {
+    Workspace &w = ws();
+    ProfScope ps("k_ing_noct_mark", s);
+    hipLaunchKernelGGL(k_ing_noct_mark, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, n, (const gf_rec *)w.rec.p,
+                       (const gf_lxc_dev *)a->d_cfgs.p, (uint32_t *)w.keys.p);
+    return hip_ok(hipGetLastError(), "k_ing_noct_mark");
+}
+
 // pack (may be empty): fills the records and bucket keys itself (the fused
 // pipeline front) instead of k_ing_pack; pout: pipeline records to complete.
 using PackFn = std::function<int(const uint16_t *slot_of, gf_rec *rec, uint32_t *keys)>;
@@ -6171,6 +6357,8 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
                        uint8_t *wsnap = nullptr, bool lru = true, bool px_keep = false, bool prepared = false,
                        const PassArgs *ta = nullptr) {
     int r;
+    const int noct = array_noct(a);                     // programs without conntrack: 0 none, 1 some, 2 all
+    if (noct && ta && ta->kind == 2) return -EOPNOTSUPP;   // (the egress entry point refuses such arrays)
     // trace notifications: the plain ingress call decides here, the pipeline and
     // egress callers (whose earlier kernels mark packets) pass their decision
     const bool tracing = ta ? ta->on : (event_ring().records && array_traces(a));
@@ -6215,7 +6403,10 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
         if ((r = hip_ok(hipGetLastError(), "k_ing_pack"))) return r;
     }
     host_mark("pack");
-    if (!prepared && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, ta && ta->kind == 2))) return r;
+    // Programs without conntrack: their packets leave the schedule (mixed array), or
+    // there is no schedule at all (every program; k_ing_noct alone, below)
+    if (noct == 1 && !prepared && (r = noct_mark(a, n, s))) return r;
+    if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, ta && ta->kind == 2))) return r;
     host_mark("sched");
     uint32_t *d_sched = (uint32_t *)w.sched.p;
     // 4. handle_policy: one bucket per lane, buckets from the longest-first queue
@@ -6240,7 +6431,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     // Non-strict mode accounts each kernel's net element change into its family's map.
     uint32_t *cnt4 = ct4m ? (uint32_t *)ct4m->d_count.p : nullptr, *cnt6 = ct6m ? (uint32_t *)ct6m->d_count.p : nullptr;
     unsigned long long *sink = (unsigned long long *)stats_sink();
-    {
+    if (noct != 2) {
         // resident-grid launches: every wave loops on its family's queue until it is drained
         uint32_t grid = resident_blocks(8);
         uint32_t need = (n + BLOCK - 1) / BLOCK;
@@ -6273,6 +6464,12 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
         }
     }
     if ((r = hip_ok(hipGetLastError(), "k_ing_groups"))) return r;
+    if (noct) {
+        ProfScope ps("k_ing_noct", s);
+        hipLaunchKernelGGL(k_ing_noct, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, X, n, noct == 2 ? 1u : 0u,
+                           (const gf_rec *)w.rec.p, out, sink);
+        if ((r = hip_ok(hipGetLastError(), "k_ing_noct"))) return r;
+    }
     host_mark("groups");
     if ((r = px_log_apply(X, s, wsnap, ev_len ? ev_len : pkts->len, ev_stride, pout ? pout : (uint8_t *)out,
                           pout != nullptr, n)))
@@ -6321,6 +6518,9 @@ static int ingress_prepare(const std::shared_ptr<PolicyArray> &a, const gf_pkt_c
                            (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p);
         if ((r = hip_ok(hipGetLastError(), "k_ing_pack"))) return r;
     }
+    const int noct = array_noct(a);
+    if (noct == 2) return 0;                            // no program with conntrack: no schedule
+    if (noct == 1 && (r = noct_mark(a, n, s))) return r;
     return schedule_groups(n, s, (const gf_rec *)w.rec.p);
 }
 
@@ -7412,6 +7612,8 @@ extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t
     if (!fr.snap || !fr.len || !out) return -EFAULT;
     if (fr.snap_stride < 34) return -EINVAL;           // an Ethernet + IPv4 header at least
     if (fr.n > (1u << 30)) return -E2BIG;
+    // the from-container program without conntrack (bpf_lxc.c:429-674 over the stub ct_*) is not built
+    if (array_noct(a)) return -EOPNOTSUPP;
     hipStream_t s = (hipStream_t)stream;
     HostMarks hm;
     CtxScope cx(s);

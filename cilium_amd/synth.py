@@ -19,6 +19,7 @@ NO_PREALLOC = 1
 # program flags (include/gpuflow.h)
 LB_L3, LB_L4, LB_REDIRECT, LB_NO_IPV4, LB_NO_IPV6 = 1, 2, 4, 8, 16
 LXC_DROP_ALL, LXC_POLICY_INGRESS, LXC_HAVE_L4_POLICY, LXC_CT_ACCOUNTING, LXC_LXC_IPV4 = 1, 2, 4, 8, 16
+LXC_NO_CONNTRACK = 128           # GF_LXC_F_NO_CONNTRACK: the endpoint's Conntrack option disabled
 LXC_PRODUCTION = LXC_POLICY_INGRESS | LXC_HAVE_L4_POLICY | LXC_CT_ACCOUNTING | LXC_LXC_IPV4
 TCP, UDP, ICMP, ICMPV6 = 6, 17, 1, 58
 F_FIN, F_SYN, F_RST, F_PSH, F_ACK = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -892,6 +893,25 @@ def conntrack_local(sc, every=1, max_entries=None):
             e[fam] = local
             made.append(local)
     return made
+
+
+def conntrack_off(sc, every=1):
+    """The Conntrack endpoint option disabled (pkg/endpoint/endpoint.go:111-114:
+    CONNTRACK undefined) on every `every`-th endpoint of the scenario: the program
+    gets GF_LXC_F_NO_CONNTRACK, binds no CT map (the stub ct_* of
+    bpf/lib/conntrack.h:582-617 take none) and loses its CFG_L3L4 lists, which
+    bpf/lib/l4.h:138-139 refuses without CONNTRACK.  Returns the affected lxc_ids."""
+    off = []
+    for j, e in enumerate(sc.lxc):
+        if j % every:
+            continue
+        e["flags"] |= LXC_NO_CONNTRACK
+        e["ct4"] = e["ct6"] = None
+        e["l4"] = []
+        if "l4e" in e:
+            e["l4e"] = []
+        off.append(e["lxc_id"])
+    return off
 
 
 def pipeline_fuzz(seed=3, n_packets=20000, n_batches=3, lb_redirect=False, fixed_secctx=None, proxy_max=524288):

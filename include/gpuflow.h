@@ -252,6 +252,17 @@ int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out,
                                                is enforced, pkg/endpoint/policy.go:820-839) */
 #define GF_LXC_F_TRACE_NOTIFY    (1u << 6)  /* TRACE_NOTIFY (pkg/endpoint/endpoint.go:131-134, on by default:
                                                daemon/main.go:629): send_trace_notify records, see below */
+#define GF_LXC_F_NO_CONNTRACK    (1u << 7)  /* CONNTRACK undefined: the endpoint's Conntrack option disabled
+                                               (pkg/endpoint/endpoint.go:111-114).  Negative sense: a clear bit keeps
+                                               conntrack.  ct_lookup / ct_create / ct_delete are the empty stubs of
+                                               bpf/lib/conntrack.h:582-617: every packet is CT_NEW, the tuple's ports
+                                               stay 0 (the policy lookup uses dport 0), no CT map is read or written.
+                                               ct_map4 / ct_map6 may be 0 and are ignored if given; GF_LXC_F_CT_ACCOUNTING
+                                               is ignored; n_l4_ingress != 0 or n_l4_egress != 0: -EINVAL
+                                               (bpf/lib/l4.h:138-139).  Such programs mix freely with the others in one
+                                               array for gf_policy_ingress_classify(_batches) and gf_pipeline_classify.
+                                               gf_lxc_egress_classify returns -EOPNOTSUPP for an array that holds one,
+                                               before any launch and without touching any state. */
 #define GF_MAX_L4_INGRESS 64
 #define GF_MAX_PORTMAP 16
 typedef struct gf_portmap {    /* struct portmap (bpf/lib/common.h), LXC_PORT_MAPPINGS entries */
