@@ -102,7 +102,7 @@ struct HTab {
     void rehash(uint64_t new_nslots);
 };
 
-enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe };
+enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay };
 
 struct Obj {
     ObjKind kind;
@@ -250,6 +250,12 @@ struct ProgPipe : Obj {
     std::shared_ptr<Map> lxc;
     std::shared_ptr<PolicyArray> policy;
     ProgPipe() : Obj(ObjKind::ProgPipe) {}
+};
+struct ProgOverlay : Obj {         // bpf_overlay.c: the program on the tunnel device
+    gf_overlay_cfg cfg{};
+    std::shared_ptr<Map> lxc;
+    std::shared_ptr<PolicyArray> policy;
+    ProgOverlay() : Obj(ObjKind::ProgOverlay) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host

@@ -112,6 +112,7 @@ enum {
     D_POLICY = -133, D_INVALID = -134, D_CT_INVALID_HDR = -135, D_CT_UNKNOWN_PROTO = -137,
     D_UNKNOWN_L3 = -139, D_MISSED_TAIL_CALL = -140, D_WRITE_ERROR = -141, D_UNKNOWN_L4 = -142,
     D_CSUM_L4 = -154, D_CT_CREATE_FAILED = -155, D_NO_SERVICE = -158, D_POLICY_L4 = -159,
+    D_NON_LOCAL = -151,
 };
 enum { CT_NEW = 0, CT_ESTABLISHED = 1, CT_REPLY = 2, CT_RELATED = 3 };
 enum { ACT_UNSPEC = 0, ACT_CREATE = 1, ACT_CLOSE = 2 };
@@ -2674,6 +2675,173 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
     if (stats) st.flush(stats);
 }
 
+// ================================================================ from-overlay
+// from_overlay of bpf/bpf_overlay.c:167-200 -> handle_ipv4 (:106-153) /
+// handle_ipv6 (:38-102), VXLAN (ENCAP_GENEVE undefined), ENABLE_IPV4: the
+// program on the tunnel device.  Each frame is the inner frame; its
+// bpf_tunnel_key.tunnel_id (the sender's identity) comes as a column.  Not
+// modelled: skb_get_tunnel_key failing (DROP_NO_TUNNEL_KEY, it cannot fail for a
+// frame the tunnel device received) and Geneve options.
+struct OvlDev {
+    gf_htab_desc lxc;
+    const uint32_t *lxset;         // cilium_lxc's IPv4 keys: address set + slots (Map::addr_set), or null
+    uint32_t lxbits, lxzero;
+    uint32_t host_ifindex;         // HOST_IFINDEX, 0 = undefined (to_host is TC_ACT_OK)
+    uint32_t host_mac[2], node_mac[2];   // HOST_IFINDEX_MAC, NODE_MAC (LE words)
+    uint32_t vec_copy;
+    uint8_t *tcap_in;              // TRACE_FROM_OVERLAY captures (128 B per packet; null: no trace)
+};
+enum { OV_TO_HOST = 1002 };
+
+__device__ int ovl_program(const OvlDev &O, Row &w, const PktHdr &h, uint32_t et, uint32_t len, uint32_t &ifx,
+                           uint32_t &lxc, uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
+    if (et == 0x0800) {
+        if (len < 34) return D_INVALID;                 // revalidate_data (:114-115)
+        uint32_t kw[5] = {w.r32(30), 0, 0, 0, 1u};      // lookup_ip4_endpoint (:123)
+        const int64_t f = O.lxset ? aset_slot(O.lxset, O.lxbits, O.lxzero, kw[0]) : ht_find<20>(O.lxc, kw, key_hash<20>(kw));
+        ab += 20;
+        if (f < 0) return D_NON_LOCAL;                  // :130-131
+        const uint8_t *ep = ht_val(O.lxc, f);
+        ab += 8;
+        const bool host = gload<uint32_t>(ep + 8) & 1u; // ENDPOINT_F_HOST (:126-127)
+        if (host && !O.host_ifindex) return TC_OK;      // HOST_IFINDEX undefined (:150-151)
+        const uint32_t ttl = w.b(22);                   // ipv4_l3 -> ipv4_dec_ttl (l3.h:54-69, ipv4.h:30-43)
+        if (ttl <= 1) return D_INVALID;
+        l3_csum(w, len, 24, ttl, ttl - 1, 2);
+        w.w8(22, ttl - 1);
+        ab += 3;
+        if (host) {                                     // to_host (:134-149)
+            w.w32(6, O.node_mac[0]); w.w16(10, O.node_mac[1]);   // eth_store_saddr(NODE_MAC)
+            w.w32(0, O.host_mac[0]); w.w16(4, O.host_mac[1]);    // eth_store_daddr(HOST_IFINDEX_MAC)
+            ab += 12;
+            return OV_TO_HOST;
+        }
+        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);   // ipv4_local_delivery (:129)
+    }
+    if (et == 0x86DD) {
+        if (len < 54) return D_INVALID;                 // :46-47
+        uint32_t kw[5] = {w.r32(38), w.r32(42), w.r32(46), w.r32(50), 2u};   // lookup_ip6_endpoint (:70)
+        const int64_t f = ht_find<20>(O.lxc, kw, key_hash<20>(kw));
+        ab += 20 + 8;
+        if (f < 0) return D_NON_LOCAL;                  // :79-80
+        const uint8_t *ep = ht_val(O.lxc, f);
+        ab += 8;
+        const bool host = gload<uint32_t>(ep + 8) & 1u;
+        if (host && !O.host_ifindex) return TC_OK;      // :99-100
+        const uint32_t hl = w.b(21);                    // ipv6_l3 -> ipv6_dec_hoplimit (l3.h:31-52, ipv6.h:178-193)
+        if (hl <= 1) return ND_ICMP6_TE;
+        w.w8(21, hl - 1);
+        ab += 1;
+        if (host) {                                     // to_host (:83-98)
+            w.w32(6, O.node_mac[0]); w.w16(10, O.node_mac[1]);
+            w.w32(0, O.host_mac[0]); w.w16(4, O.host_mac[1]);
+            ab += 12;
+            return OV_TO_HOST;
+        }
+        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);   // ipv6_local_delivery (:78)
+    }
+    return TC_OK;                                       // unknown traffic to the stack (:191-193)
+}
+
+// The sibling of k_pipe_front for the tunnel device: one packet per lane over
+// its frame in LDS (NT * snap_stride bytes of dynamic shared memory, <= 32 KiB:
+// five blocks per CU, so the kernel is not held to k_pipe_front's 64 VGPRs),
+// the handle_policy record and flow-group key written directly for ingress_run.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *tunnel_id, const uint8_t *tc_index,
+                                                  OvlDev O, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
+                                                  uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
+                                                  uint8_t *snap_out, unsigned long long *stats) {
+    extern __shared__ uint4 lds_rows[];
+    uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
+    __shared__ uint32_t sl[272];
+    Stats st{sl};
+    if (stats) st.init();
+    const uint32_t S = fr.snap_stride;
+    const uint32_t b0 = blockIdx.x * NT;
+    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
+    const size_t bytes = (size_t)nb * S;
+    {
+        const uint8_t *src = fr.snap + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (O.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
+    }
+    __syncthreads();
+    const uint32_t i = b0 + threadIdx.x;
+    bool scnt = false;                                  // the lane's counter-block entry
+    uint32_t sreason = 0, saction = 0, slen = 0, sab = 0;
+    if (i < fr.n) {
+        const uint32_t len = fr.len[i];
+        const uint32_t cap = S < len ? S : len;
+        Row w{rows + (size_t)threadIdx.x * S, cap};
+        PktHdr h;
+        parse_row(w.p, cap, len, h);
+        const uint32_t et = h.et;
+        gf_pipeline_out o{};
+        uint32_t ifx = 0, lxc = 0, mapped = 0, ndport = 0;
+        uint32_t ab = 24 + 34 + 4;                      // output record, header bytes parsed, tunnel id
+        if (O.tcap_in) {                                // from_overlay's send_trace_notify (:174): the frame as received
+            uint8_t *d = O.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
+            const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
+            if (O.vec_copy) {
+                for (uint32_t k = 0; k < cb; k += 16)
+                    *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
+            } else {
+                for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
+            }
+        }
+        const int r = ovl_program(O, w, h, et, len, ifx, lxc, mapped, ndport, ab);
+        if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
+        o.stage = GF_STAGE_OVERLAY;
+        const bool tail = r == ND_TAILCALL;
+        if (tail) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; }
+        else if (r == OV_TO_HOST) { o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)O.host_ifindex; }
+        else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
+        else if (r < 0) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }   // send_drop_notify_error (:159-160, :196-197)
+        else o.action = (uint8_t)r;
+        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
+        gf_rec rr;
+        uint32_t key;
+        const uint32_t tci = tc_index ? tc_index[i] : 0u;
+        if (tail) {
+            PktHdr h2;
+            parse_row(w.p, cap, len, h2);
+            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, tunnel_id[i], ifx,
+                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr);
+            rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);   // the front's flags for IngCtx::pout_wo, as k_pipe_front
+            if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
+                reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
+                reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
+            }
+        } else {
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr);
+        }
+        rec[i] = rr;
+        keys[i] = key;
+        out[i] = o;
+        sab = ab;                                       // a tail-called packet: handle_policy counts it
+        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
+    }
+    if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
+    if (snap_out) {
+        __syncthreads();
+        uint8_t *dst = snap_out + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (O.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
+    }
+    if (stats) st.flush(stats);
+}
+
 // ---- ingest re-partition (real traffic on N GPUs): the owner rank of each
 // frame is the rank of its flow group, the unordered address pair that the
 // CT of handle_policy sees, i.e. after bpf_lb's translation (stateless, so it
@@ -3424,7 +3592,8 @@ struct EvSrc {
     const uint8_t *tcap_in;   // pipeline: TRACE_FROM_STACK captures
     const uint8_t *orig;      // egress: the frames as sent (TRACE_FROM_LXC), snap_stride apart
     const uint16_t *lxc_id, *slot_of;   // egress: the sender's program
-    uint32_t host_ifindex, encap_ifindex, nd_trace, nd_ifindex;
+    uint32_t host_ifindex, encap_ifindex, nd_trace, nd_ifindex;   // nd_trace: 0, or the front program's observation
+                                                                  // point | its own final stage << 8
 };
 // One notification: the 8 header words of struct drop_notify / trace_notify and
 // where its captured bytes come from.
@@ -3446,13 +3615,13 @@ __device__ __forceinline__ EvOne ev_trace(uint32_t obs, uint32_t source, uint32_
     return e;
 }
 enum { TR_TO_LXC = 0, TR_TO_PROXY = 1, TR_TO_HOST = 2, TR_TO_STACK = 3, TR_TO_OVERLAY = 4, TR_FROM_LXC = 5,
-       TR_FROM_STACK = 8 };
+       TR_FROM_STACK = 8, TR_FROM_OVERLAY = 9 };
 // The notifications of packet i in the order the programs send them (k < 0:
 // just count them).  Drops: send_drop_notify / __send_drop_notify (drop.h:47-107)
 // after handle_policy (src_label, SECLABEL, LXC_ID, ifindex), the sender's
 // (SECLABEL, 0, 0, 0) after the from-container program, zeros for the callers'
 // send_drop_notify_error.  Traces: from_netdev's TRACE_FROM_STACK
-// (bpf_netdev.c:436), handle_ingress's TRACE_FROM_LXC (bpf_lxc.c:705), the
+// (bpf_netdev.c:436) or from_overlay's TRACE_FROM_OVERLAY (bpf_overlay.c:174), handle_ingress's TRACE_FROM_LXC (bpf_lxc.c:705), the
 // redirects' TRACE_TO_PROXY (lxc.h:116/168), TO_HOST / TO_STACK / TO_OVERLAY
 // of the from-container exits (bpf_lxc.c:364,381,650,669, encap.h:67) and
 // handle_policy's TRACE_TO_LXC when it did not redirect (bpf_lxc.c:1013-1016).
@@ -3468,8 +3637,8 @@ __device__ uint32_t ev_list(const EvSrc &E, uint32_t i, int k, EvOne &out) {
     uint32_t n = 0;
     auto put = [&](const EvOne &e) { if ((int)n == k) out = e; n++; };
     if (E.trace) {
-        if (E.kind == 1 && E.nd_trace && (stage == GF_STAGE_NETDEV || stage == GF_STAGE_POLICY))
-            put(ev_trace(TR_FROM_STACK, 0, hash, len, 0, 0, 0, E.nd_ifindex, 0,
+        if (E.kind == 1 && E.nd_trace && (stage == (E.nd_trace >> 8) || stage == GF_STAGE_POLICY))
+            put(ev_trace(E.nd_trace & 0xffu, 0, hash, len, 0, 0, 0, E.nd_ifindex, 0,
                          E.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN, GF_TRACE_PAYLOAD_LEN));
         if (E.kind == 2) {
             const uint32_t sl = E.slot_of[E.lxc_id ? E.lxc_id[i] : 0];
@@ -5606,7 +5775,8 @@ struct PassArgs {                  // what the pipeline / egress callers pass to
     const uint32_t *rlog_off;      // device word: the run fell back to pair groups (the log is not used)
     RelSet rs;                     // GF_EG_RSET: the related entries' set (rlog then only marks it in use)
     bool on;                       // this call traces (a ring is set and a program / the netdev traces)
-    uint32_t nd_trace, nd_ifindex; // pipeline: GF_NETDEV_F_TRACE_NOTIFY, skb->ingress_ifindex
+    uint32_t nd_trace, nd_ifindex; // pipeline / overlay: 0, or the front's observation point | its final stage << 8
+                                   // (EvSrc::nd_trace); skb->ingress_ifindex
     const uint8_t *orig;           // egress: the frames as sent
     const uint16_t *lxc_id;        // egress: the senders
 };
@@ -6704,7 +6874,7 @@ int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_
     P.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
     PassArgs ta{};
     ta.kind = 1;
-    ta.nd_trace = (p->cfg.netdev.flags & GF_NETDEV_F_TRACE_NOTIFY) ? 1u : 0u;
+    ta.nd_trace = (p->cfg.netdev.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_STACK | (GF_STAGE_NETDEV << 8)) : 0u;
     ta.nd_ifindex = p->cfg.netdev.ingress_ifindex;
     ta.on = event_ring().records && (ta.nd_trace || array_traces(p->policy));
     if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
@@ -6723,6 +6893,86 @@ int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_
             hipLaunchKernelGGL(k_pipe_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tc_index, b->flow_hash, P,
                                slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
         return hip_ok(hipGetLastError(), "k_pipe_front");
+    };
+    c2.flow_hash = b->flow_hash;
+    return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
+                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+}
+
+// ---- from-overlay ----
+int gf_overlay_load(const gf_overlay_cfg *cfg) {
+    std::unique_lock<std::shared_mutex> g(prog_lock());
+    if (!cfg) return -EFAULT;
+    auto p = std::make_shared<ProgOverlay>();
+    p->cfg = *cfg;
+    auto m = get_map(cfg->lxc_map);
+    if (!m) return -EBADF;
+    if (m->ksz != 20 || m->vsz != 112 || m->is_lpm()) return -EINVAL;
+    p->lxc = m;
+    auto a = get_obj(cfg->policy_array);
+    if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
+    p->policy = std::static_pointer_cast<PolicyArray>(a);
+    return new_handle(p);
+}
+
+int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf_pipeline_out *out,
+                        uint8_t *snap_out, void *stream) {
+    std::shared_lock<std::shared_mutex> g(prog_lock());
+    auto o = get_obj(ovl);
+    if (!o || o->kind != ObjKind::ProgOverlay) return -EBADF;
+    auto p = std::static_pointer_cast<ProgOverlay>(o);
+    if (!b) return -EFAULT;
+    const gf_frames &fr = b->frames;
+    if (fr.n == 0) return 0;
+    if (!fr.snap || !fr.len || !out || !b->tunnel_id) return -EFAULT;
+    if (fr.snap_stride < 14 || fr.snap_stride > 256) return -EINVAL;   // a header snap, staged in LDS
+    if (fr.n > (1u << 30)) return -E2BIG;
+    hipStream_t s = (hipStream_t)stream;
+    HostMarks hm;
+    CtxScope cx(s);
+    std::lock_guard<std::mutex> ag(p->policy->mu);
+    MapLocks L;
+    L.add(p->lxc);
+    lock_array_maps(L, p->policy);
+    L.lock();
+    CallOrder co(s, L, p->policy.get());
+    int r;
+    const uint32_t n = fr.n;
+    OvlDev O{};
+    if ((r = push_map(p->lxc, s))) return r;
+    O.lxc = p->lxc->hdesc();
+    if (getenv("GF_XDP_NOSETS") || p->lxc->addr_set(20, 8192, s, &O.lxset, &O.lxbits, &O.lxzero)) O.lxset = nullptr;
+    const gf_node_cfg &node = node_cfg();
+    O.host_ifindex = node.host_ifindex;
+    memcpy(O.host_mac, node.host_mac, 6); memcpy(O.node_mac, node.node_mac, 6);
+    // LDS staging as k_pipe_front: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B (<= 32 KiB)
+    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
+    const size_t lds = (size_t)nt * fr.snap_stride;
+    PipeWs &w = pipe_ws();
+    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
+    if ((r = grow(w.s6, (size_t)n * 32))) return r;    // saddr6 | daddr6 per packet (IngCtx::a6_stride 32)
+    O.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
+    PassArgs ta{};
+    ta.kind = 1;                                       // records completed as the pipeline's
+    ta.nd_trace = (p->cfg.flags & GF_OVERLAY_F_TRACE_NOTIFY) ? (TR_FROM_OVERLAY | (GF_STAGE_OVERLAY << 8)) : 0u;
+    ta.nd_ifindex = p->cfg.ingress_ifindex;
+    ta.on = event_ring().records && (ta.nd_trace || array_traces(p->policy));
+    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
+    if (ta.on && ta.nd_trace) O.tcap_in = (uint8_t *)trace_ws().in.p;
+    unsigned long long *sink = (unsigned long long *)stats_sink();
+    const uint32_t grid = (n + nt - 1) / nt;         // one NT-frame tile per block
+    gf_pkt_cols c2{};
+    c2.n = n;
+    c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
+    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
+        ProfScope ps("k_ovl_front", s);
+        if (nt == 256)
+            hipLaunchKernelGGL(k_ovl_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+        else
+            hipLaunchKernelGGL(k_ovl_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+        return hip_ok(hipGetLastError(), "k_ovl_front");
     };
     c2.flow_hash = b->flow_hash;
     return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,

@@ -16,7 +16,8 @@ import numpy as np
 
 from . import bpf
 from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
-                   gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch)
+                   gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
+                   gf_overlay_batch)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
                    ("rev_nat", "<u2"), ("new_daddr4", "<u4")])
@@ -96,6 +97,7 @@ class DeviceBatch:
         self.lxc_id = t(pk.lxc_id, np.uint16)
         self.tc_index = t(pk.tc_index, np.uint8)
         self.flow_hash = t(pk.flow_hash, np.uint32)
+        self.tunnel_id = t(getattr(pk, "tunnel_id", None), np.uint32)   # bpf_tunnel_key.tunnel_id (from-overlay)
         n = self.n
         e = lambda dt, *shape: torch.empty((n,) + shape, dtype=dt, device=device)
         self.ethertype = e(torch.int16)
@@ -201,6 +203,13 @@ class Datapath:
             pcfg = gf_pipeline_cfg(self.xdp_prog or 0, self.lb_prog or 0, ncfg, self.policy_array)
             self.pipe = _check(lib.gf_pipeline_load(C.byref(pcfg)), "gf_pipeline_load")
 
+        # the program on the tunnel device (bpf_overlay.c), sc.overlay = {lxc_map, flags, ingress_ifindex}
+        self.ovl = None
+        if getattr(sc, "overlay", None) and self.policy_array:
+            ov = sc.overlay
+            ocfg = gf_overlay_cfg(h(ov["lxc_map"]), ov.get("flags", 0), ov.get("ingress_ifindex", 0), self.policy_array)
+            self.ovl = _check(lib.gf_overlay_load(C.byref(ocfg)), "gf_overlay_load")
+
     # ---- classify calls -------------------------------------------------
     def xdp(self, b):
         torch = _torch()
@@ -255,6 +264,20 @@ class Datapath:
                "gf_pipeline_classify")
         return out, nd6, snap
 
+    def overlay(self, b, now, out=None, snap_out=True):
+        """from-overlay over the batch's inner frames and tunnel ids (+ handle_policy of
+        the local deliveries): returns (records [n,24] u8, rewritten snaps or None)."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty((b.n, 24), dtype=torch.uint8, device=b.device)
+        snap = torch.empty_like(b.frames) if snap_out else None
+        stride = b.frames.shape[1] if b.n else 64
+        ob = gf_overlay_batch(gf_frames(b.n, stride, _ptr(b.frames), _ptr(b.len)), _ptr(b.tunnel_id), _ptr(b.tc_index),
+                              _ptr(b.flow_hash))
+        _check(lib.gf_overlay_classify(self.ovl, C.byref(ob), now, _ptr(out), _ptr(snap), _stream()),
+               "gf_overlay_classify")
+        return out, snap
+
     def egress(self, b, now, out=None, snap_out=True):
         """The from-container program over the batch's frames (+ handle_policy of the
         local deliveries): returns (records [n,24] u8, rewritten snaps or None)."""
@@ -280,13 +303,13 @@ class Datapath:
     def close(self):
         """Close the program objects, then the maps (a program holds its maps, so
         their device tables are released once both are closed)."""
-        progs = [self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
+        progs = [self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
         for h in [h for h in progs if h] + list(self.fd.values()):
             try:
                 bpf.ObjClose(h)
             except OSError:
                 pass
-        self.pipe = self.policy_array = self.lb_prog = self.xdp_prog = None
+        self.ovl = self.pipe = self.policy_array = self.lb_prog = self.xdp_prog = None
         self.lxc_progs = []
         self.fd = {}
 

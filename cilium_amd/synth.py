@@ -49,6 +49,7 @@ class Packets:
     lxc_id: np.ndarray = None
     tc_index: np.ndarray = None
     flow_hash: np.ndarray = None
+    tunnel_id: np.ndarray = None  # bpf_tunnel_key.tunnel_id per frame (from-overlay batches)
 
     @property
     def n(self):
@@ -57,7 +58,7 @@ class Packets:
     def slice(self, a, b):
         f = lambda x: None if x is None else x[a:b]
         return Packets(self.frames[a:b], self.lens[a:b], f(self.src_identity), f(self.ifindex), f(self.lxc_id),
-                       f(self.tc_index), f(self.flow_hash))
+                       f(self.tc_index), f(self.flow_hash), f(self.tunnel_id))
 
 
 @dataclass
@@ -73,6 +74,7 @@ class Scenario:
     batches: list = field(default_factory=list)   # list of Packets, processed in order
     now: int = 1000
     meta: dict = field(default_factory=dict)
+    overlay: dict = None         # bpf_overlay config (gf_overlay_cfg): {'lxc_map','flags','ingress_ifindex'}
 
     def add_map(self, spec):
         self.maps[spec.name] = spec
@@ -990,6 +992,37 @@ def pipeline_fuzz(seed=3, n_packets=20000, n_batches=3, lb_redirect=False, fixed
                "host_ip6": bytes([0xbe, 0xef, 0, 0, 0, 0, 0, 0, 0, 0, 0xa, 0, 0x2, 0xf, 0xff, 0xff]),
                "host_mac": bytes([0xce, 0x72, 0xa7, 0x03, 0x88, 0x56]),
                "node_mac": bytes([0xde, 0xad, 0xbe, 0xef, 0xc0, 0xde])}
+    return sc
+
+
+def overlay_fuzz(seed=3, n_packets=20000, n_batches=3, strangers=0.1, to_host=0.12, **kw):
+    """pipeline_fuzz's frames as the tunnel device receives them (bpf_overlay.c): each
+    batch gets a tunnel_id column — the batch's identity column (identities the policy
+    maps hold), `strangers` of it replaced by identities no map holds — and `to_host`
+    of the IP frames are readdressed to a host entry of cilium_lxc (the to_host branch;
+    the VIPs that are host entries go there too, the other VIPs, replies and random
+    destinations are DROP_NON_LOCAL).  HOST_IFINDEX is defined (non-zero)."""
+    sc = pipeline_fuzz(seed, n_packets, n_batches, **kw)
+    sc.name = f"ovl{seed}"
+    rng = np.random.default_rng(seed ^ 0x0E1A)
+    lxc = sc.maps["cilium_lxc"]
+    host = lxc.vals[:, 8] & 1
+    h4 = lxc.keys[(host == 1) & (lxc.keys[:, 16] == 1)][:, :4]
+    h6 = lxc.keys[(host == 1) & (lxc.keys[:, 16] == 2)][:, :16]
+    for k, pk in enumerate(sc.batches):
+        f = pk.frames
+        et = (f[:, 12].astype(np.uint32) << 8) | f[:, 13]
+        pick = rng.random(pk.n) < to_host
+        r4 = np.nonzero(pick & (et == 0x0800))[0]
+        f[r4, 30:34] = h4[rng.integers(0, len(h4), len(r4))]
+        r6 = np.nonzero(pick & (et == 0x86DD))[0]
+        f[r6, 38:54] = h6[rng.integers(0, len(h6), len(r6))]
+        tid = pk.src_identity.astype(np.uint32).copy()
+        st = rng.random(pk.n) < strangers
+        tid[st] = rng.integers(1000, 1 << 24, int(st.sum()))
+        sc.batches[k] = Packets(f, pk.lens, pk.src_identity, pk.ifindex, pk.lxc_id, pk.tc_index, pk.flow_hash, tid)
+    assert sc.host_ifindex
+    sc.overlay = {"lxc_map": "cilium_lxc", "flags": 0, "ingress_ifindex": 9}
     return sc
 
 

@@ -33,6 +33,8 @@
  *     gf_policy_ingress_classify <- handle_policy/ipv{4,6}_policy bpf/bpf_lxc.c:745-1024
  *     gf_lxc_egress_classify     <- from-container handle_ingress bpf/bpf_lxc.c:427-738
  *     gf_pipeline_classify       <- bpf_xdp -> bpf_lb -> bpf_netdev -> cilium_policy tail call
+ *     gf_overlay_classify        <- from_overlay (tunnel receive) bpf/bpf_overlay.c:38-200 -> cilium_policy
+ *                                   tail call (VXLAN; no DROP_NO_TUNNEL_KEY, no Geneve options)
  *     gf_parse_frames            <- the skb_load_bytes()/revalidate_data() header
  *                                   accesses of those programs (bpf/lib/common.h:67-87,
  *                                   bpf/lib/ipv4.h:45-48, bpf/lib/ipv6.h:61-98)
@@ -482,6 +484,57 @@ typedef struct gf_pipeline_out {   /* 24 B */
 int gf_pipeline_classify(int pipe, const gf_pipe_batch *batch, uint32_t now_sec, gf_pipeline_out *out,
                          uint8_t *new_daddr6, uint8_t *snap_out, void *stream);
 
+/* ---- from-overlay: the program on the tunnel device (bpf/bpf_overlay.c:38-200) ----
+ * In tunnel mode every cross-node pod-to-pod packet reaches its endpoint
+ * through this program: the frames gf_lxc_egress_classify reports with
+ * GF_EG_F_ENCAP on the sending node, as the VXLAN device hands their inner
+ * frame to tc on the receiving one, with bpf_tunnel_key.tunnel_id = the
+ * sender's security identity.  ENCAP_GENEVE undefined, ENABLE_IPV4 defined.
+ *   0x0800: len < 34 DROP_INVALID; lookup_ip4_endpoint(daddr) in cilium_lxc:
+ *           no entry DROP_NON_LOCAL; ENDPOINT_F_HOST -> to_host: ipv4_l3(NODE_MAC,
+ *           HOST_IFINDEX_MAC) (TTL <= 1 DROP_INVALID) and redirect(HOST_IFINDEX), or
+ *           TC_ACT_OK with the frame untouched when HOST_IFINDEX is undefined
+ *           (gf_node_cfg.host_ifindex == 0); else ipv4_local_delivery with
+ *           seclabel = tunnel_id and the cilium_policy tail call
+ *   0x86DD: len < 54 DROP_INVALID; the same three outcomes with ipv6_l3 (hop limit
+ *           <= 1: icmp6_send_time_exceeded, reported as action REDIRECT with
+ *           GF_PIPE_F_ICMP6_TE) and ipv6_local_delivery; no icmp6_handle, no
+ *           derive_sec_ctx
+ *   other:  TC_ACT_OK
+ * Errors end in send_drop_notify_error(skb, ret, TC_ACT_SHOT).  Not modelled:
+ * skb_get_tunnel_key failing (DROP_NO_TUNNEL_KEY: it cannot for a frame received
+ * from the tunnel device) and Geneve options.
+ * Records are gf_pipeline_out: stage GF_STAGE_OVERLAY for the verdicts the program
+ * itself ends (to_host: action REDIRECT, ifindex_lo = HOST_IFINDEX), stage
+ * GF_STAGE_POLICY for tail-called packets, completed by handle_policy as in the
+ * pipeline (lxc_id, ct_ret, flags, proxy_port, ifindex_lo, GF_PIPE_F_PORTMAP with
+ * dport); slave, rev_nat and daddr4 stay 0.  HOST_IFINDEX, HOST_IFINDEX_MAC and
+ * NODE_MAC come from gf_node_config.  With an event ring set, drops are recorded as
+ * the pipeline records them and GF_OVERLAY_F_TRACE_NOTIFY makes each packet's first
+ * record TRACE_FROM_OVERLAY (subtype 9, ifindex = ingress_ifindex, the frame as
+ * received; bpf_overlay.c:174). */
+#define GF_DROP_NON_LOCAL 151      /* DROP_NON_LOCAL, bpf/lib/common.h:245 */
+#define GF_STAGE_OVERLAY  6        /* the from-overlay verdict is final */
+#define GF_OVERLAY_F_TRACE_NOTIFY (1u << 0)
+typedef struct gf_overlay_cfg {
+    int lxc_map;                   /* cilium_lxc */
+    uint32_t flags;                /* GF_OVERLAY_F_* */
+    uint32_t ingress_ifindex;      /* the tunnel device's ifindex (TRACE_FROM_OVERLAY) */
+    int policy_array;              /* cilium_policy prog array */
+} gf_overlay_cfg;
+int gf_overlay_load(const gf_overlay_cfg *cfg);
+typedef struct gf_overlay_batch {
+    gf_frames frames;              /* DEVICE inner frames, snap_stride 14..256 as the pipeline */
+    const uint32_t *tunnel_id;     /* DEVICE, bpf_tunnel_key.tunnel_id per frame; required */
+    const uint8_t  *tc_index;      /* DEVICE, may be NULL */
+    const uint32_t *flow_hash;     /* DEVICE, may be NULL (the event records' hash) */
+} gf_overlay_batch;
+/* snap_out (n * snap_stride, may be NULL): every frame as rewritten before
+ * handle_policy.  -EBADF, -EFAULT (a NULL batch, frame pointer, out or tunnel_id),
+ * -EINVAL (snap_stride < 14 or > 256), -E2BIG; n == 0 returns 0. */
+int gf_overlay_classify(int ovl, const gf_overlay_batch *batch, uint32_t now_sec,
+                        gf_pipeline_out *out, uint8_t *snap_out, void *stream);
+
 /* ---- ingest re-partition for N GPUs (real traffic) ----
  * owner[i] = the rank owning packet i's flow group: the unordered address pair
  * handle_policy's conntrack sees (after bpf_lb's translation, which is
@@ -548,7 +601,8 @@ int gf_ct_evict_log(int map, gf_ct_evict_rec *out, uint32_t max);
  * Programs loaded with GF_LXC_F_TRACE_NOTIFY (and a pipeline whose netdev has
  * GF_NETDEV_F_TRACE_NOTIFY) also append struct trace_notify records to the same
  * ring (type CILIUM_NOTIFY_TRACE=4, subtype = observation point TRACE_TO_LXC 0,
- * TO_PROXY 1, TO_HOST 2, TO_STACK 3, TO_OVERLAY 4, FROM_LXC 5, FROM_STACK 8;
+ * TO_PROXY 1, TO_HOST 2, TO_STACK 3, TO_OVERLAY 4, FROM_LXC 5, FROM_STACK 8, FROM_OVERLAY 9
+ * (gf_overlay_classify with GF_OVERLAY_F_TRACE_NOTIFY);
  * source = EVENT_SOURCE, hash, len_orig, len_cap, src_label, dst_label, dst_id
  * (u16), reason (the CT result that forwarded it), pad, ifindex — the layout
  * pkg/monitor/datapath_trace.go TraceNotify decodes), followed by the first
