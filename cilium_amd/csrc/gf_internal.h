@@ -102,7 +102,7 @@ struct HTab {
     void rehash(uint64_t new_nslots);
 };
 
-enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay };
+enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost };
 
 struct Obj {
     ObjKind kind;
@@ -256,6 +256,12 @@ struct ProgOverlay : Obj {         // bpf_overlay.c: the program on the tunnel d
     std::shared_ptr<Map> lxc;
     std::shared_ptr<PolicyArray> policy;
     ProgOverlay() : Obj(ObjKind::ProgOverlay) {}
+};
+struct ProgHost : Obj {            // bpf_netdev.c with FROM_HOST: the program on cilium_host
+    gf_host_cfg cfg{};
+    std::shared_ptr<Map> lxc;
+    std::shared_ptr<PolicyArray> policy;
+    ProgHost() : Obj(ObjKind::ProgHost) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host

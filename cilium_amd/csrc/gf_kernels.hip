@@ -2842,6 +2842,267 @@ __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *
     if (stats) st.flush(stats);
 }
 
+// ================================================================ from-host
+// from_netdev of bpf/bpf_netdev.c:414-468 -> handle_ipv4 (:328-396) / handle_ipv6
+// (:163-246) compiled with FROM_HOST and ENABLE_IPV4, without HANDLE_NS; ENCAP_IFINDEX
+// is defined iff encap_ifindex != 0: the program on cilium_host.  skb->mark comes as
+// a column; its reset to 0 (:143) has no output.  The reverse lookups read
+// cilium_proxy{4,6} as they stand when the kernel runs, which is before
+// handle_policy of the same call inserts anything (the inserts are applied after
+// k_ing_groups, see px_log_apply).
+struct HostDev {
+    gf_htab_desc lxc, px4, px6, tunnel;
+    const uint32_t *lxset, *tnset; // cilium_lxc's / the tunnel map's IPv4 keys (Map::addr_set), or null
+    uint32_t lxbits, lxzero, tnbits, tnzero;
+    uint32_t flags, fixed_secctx;  // GF_NETDEV_F_*, FIXED_SRC_SECCTX
+    uint32_t router6[2];           // first 8 bytes of the netdev's ROUTER_IP (derive_sec_ctx)
+    uint32_t node6[3];             // first 12 bytes of gf_node_cfg.router_ip6 (ipv6_match_prefix_96)
+    uint32_t net_mac[2];           // CILIUM_NET_MAC (LE words)
+    uint32_t encap_ifindex, cluster_range, cluster_mask, ipv4_mask;
+    uint32_t vec_copy;
+    uint8_t *tcap_in;              // TRACE_FROM_HOST / FROM_PROXY captures (128 B per packet; null: no trace)
+};
+enum { HO_ENCAP = 1003 };
+enum { MARK_MAGIC_PROXY_MASK = 0xFFF, MARK_MAGIC_PROXY_INGRESS = 0xFEA, MARK_MAGIC_PROXY_EGRESS = 0xFEB };
+
+// handle_identity_from_proxy (:128-145): the identity the proxy put into the mark
+// (0: none), skip = TC_INDEX_F_SKIP_PROXY for the ingress proxy's packets.
+__device__ __forceinline__ uint32_t host_mark_identity(uint32_t mark, uint32_t &skip) {
+    const uint32_t magic = mark & MARK_MAGIC_PROXY_MASK;
+    skip = magic == MARK_MAGIC_PROXY_INGRESS ? 1u : 0u;
+    return (magic == MARK_MAGIC_PROXY_INGRESS || magic == MARK_MAGIC_PROXY_EGRESS) ? mark >> 16 : 0u;
+}
+
+// reverse_proxy (:264-325) / reverse_proxy6 (:67-124); nh is the IP header's own
+// next-header byte (an IPv6 frame with an extension header is ignored).  rev: the
+// translation was applied.
+__device__ int host_reverse_proxy(const HostDev &H, Row &w, uint32_t len, bool v6, int l4_off, uint32_t nh,
+                                  uint32_t &rev, uint32_t &ab) {
+    if (nh != 6 && nh != 17) return 0;
+    if (!skb_ok(l4_off, 4, len)) return D_CT_INVALID_HDR;
+    const uint32_t ports = w.r32((uint32_t)l4_off);     // key.dport = the packet's sport, key.sport = its dport
+    const uint32_t co = csum_l4_offset(nh), fl = nh == 17 ? GF_F_MANGLED_0 : 0u;
+    ab += 4;
+    if (!v6) {
+        uint32_t kw[3] = {w.r32(30), ports, nh};        // .saddr = ip4->daddr
+        const int64_t f = ht_find<10>(H.px4, kw, key_hash<10>(kw));
+        ab += 10;
+        if (f < 0) return 0;
+        const uint8_t *v = ht_val(H.px4, f);
+        const uint32_t new_saddr = gload<uint32_t>(v), new_sport = gload<uint16_t>(v + 4);
+        const uint32_t old_saddr = w.r32(26), old_sport = ports & 0xffffu;
+        ab += 16;
+        if (l4_csum(w, len, l4_off + (int)co, old_sport, new_sport, 2u | fl) < 0) return D_WRITE_ERROR;   // l4_modify_port
+        w.w16((uint32_t)l4_off, new_sport);
+        w.w32(26, new_saddr);
+        l3_csum(w, len, 24, old_saddr, new_saddr, 4);
+        l4_csum(w, len, l4_off + (int)co, old_saddr, new_saddr, 4u | GF_F_PSEUDO_HDR | fl);
+        ab += 2 + 4 + 2 + 2;
+    } else {
+        uint32_t kw[6] = {w.r32(38), w.r32(42), w.r32(46), w.r32(50), ports, nh};   // .saddr = ip6->daddr
+        const int64_t f = ht_find<22>(H.px6, kw, key_hash<22>(kw));
+        ab += 22;
+        if (f < 0) return 0;
+        const uint8_t *v = ht_val(H.px6, f);
+        const uint32_t new_sport = gload<uint16_t>(v + 16), old_sport = ports & 0xffffu;
+        ab += 28;
+        if (l4_csum(w, len, l4_off + (int)co, old_sport, new_sport, 2u | fl) < 0) return D_WRITE_ERROR;   // l4_modify_port
+        w.w16((uint32_t)l4_off, new_sport);
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {                   // ipv6_store_saddr + csum_diff(old, 16, new, 16, 0)
+            const uint32_t o = w.r32(22 + 4 * k), nw = gload<uint32_t>(v + 4 * k);
+            w.w32(22 + 4 * k, nw);
+            sum = ck_add(ck_add(sum, ~o), nw);
+        }
+        l4_csum(w, len, l4_off + (int)co, 0, sum, GF_F_PSEUDO_HDR | fl);
+        ab += 2 + 16 + 2;
+    }
+    rev = 1;
+    return 0;
+}
+
+__device__ int host_program(const HostDev &H, Row &w, const PktHdr &h, uint32_t et, uint32_t len, uint32_t pid,
+                            uint32_t &sec, uint32_t &rev, uint32_t &tun_ip, uint32_t &ifx, uint32_t &lxc,
+                            uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
+    if (et == 0x0800) {
+        if (len < 34) return D_INVALID;                 // revalidate_data (:337-338)
+        sec = (H.flags & GF_NETDEV_F_FIXED_SECCTX) ? H.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
+        if (pid) sec = pid;                             // :348-349
+        const int rr = host_reverse_proxy(H, w, len, false, h.l4, w.b(23), rev, ab);   // :351
+        if (rr < 0) return rr;
+        w.w32(0, H.net_mac[0]); w.w16(4, H.net_mac[1]); // rewrite_dmac_to_host (:358)
+        ab += 6;
+        const uint32_t da = w.r32(30);
+        uint32_t kw[5] = {da, 0, 0, 0, 1u};             // lookup_ip4_endpoint (:369)
+        const int64_t f = H.lxset ? aset_slot(H.lxset, H.lxbits, H.lxzero, kw[0]) : ht_find<20>(H.lxc, kw, key_hash<20>(kw));
+        ab += 20;
+        if (f >= 0) {
+            const uint8_t *ep = ht_val(H.lxc, f);
+            ab += 8;
+            if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;   // ENDPOINT_F_HOST (:372-373)
+            const uint32_t ttl = w.b(22);               // ipv4_local_delivery (:375): ipv4_dec_ttl
+            if (ttl <= 1) return D_INVALID;
+            l3_csum(w, len, 24, ttl, ttl - 1, 2);
+            w.w8(22, ttl - 1);
+            ab += 3;
+            return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+        }
+        if (H.encap_ifindex && (da & H.cluster_mask) == H.cluster_range) {   // ENCAP_IFINDEX (:378-393)
+            uint32_t tk[5] = {da & H.ipv4_mask, 0, 0, 0, 1u};
+            const int64_t ft = H.tnset ? aset_slot(H.tnset, H.tnbits, H.tnzero, tk[0]) : ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
+            ab += 20;
+            if (ft >= 0) {                              // encap_and_redirect (lib/encap.h:30-70)
+                tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
+                ab += 20;
+                return HO_ENCAP;
+            }
+        }
+        return TC_OK;                                   // :395
+    }
+    if (et == 0x86DD) {
+        if (len < 54) return D_INVALID;                 // :174-175
+        sec = 2u;                                       // derive_sec_ctx (:50-64)
+        if (H.flags & GF_NETDEV_F_FIXED_SECCTX) sec = H.fixed_secctx;
+        else if (w.r32(22) == H.router6[0] && w.r32(26) == H.router6[1])
+            sec = __builtin_bswap32(w.r32(14) & __builtin_bswap32(0x000FFFFFu));
+        if (pid) sec = pid;                             // :195-196
+        const int rr = host_reverse_proxy(H, w, len, true, h.l4, w.b(20), rev, ab);   // :198, ip6->nexthdr
+        if (rr < 0) return rr;
+        w.w32(0, H.net_mac[0]); w.w16(4, H.net_mac[1]); // rewrite_dmac_to_host (:205)
+        ab += 6;
+        const uint32_t d0 = w.r32(38), d1 = w.r32(42), d2 = w.r32(46);
+        uint32_t kw[5] = {d0, d1, d2, w.r32(50), 2u};   // lookup_ip6_endpoint (:216)
+        const int64_t f = ht_find<20>(H.lxc, kw, key_hash<20>(kw));
+        ab += 20 + 8;
+        if (f >= 0) {
+            const uint8_t *ep = ht_val(H.lxc, f);
+            ab += 8;
+            if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;   // :219-220
+            const uint32_t hl = w.b(21);                // ipv6_local_delivery (:222): ipv6_dec_hoplimit
+            if (hl <= 1) return ND_ICMP6_TE;
+            w.w8(21, hl - 1);
+            ab += 1;
+            return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+        }
+        if (H.encap_ifindex && d0 == H.node6[0] && d1 == H.node6[1] && d2 == H.node6[2]) {   // :225-243
+            uint32_t tk[5] = {d0, d1, d2, 0u, 2u};      // daddr/96
+            const int64_t ft = ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
+            ab += 20;
+            if (ft >= 0) {
+                tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
+                ab += 20;
+                return HO_ENCAP;
+            }
+        }
+        return TC_OK;                                   // :245
+    }
+    return TC_OK;                                       // unknown traffic to the stack (:462-464)
+}
+
+// The sibling of k_ovl_front for cilium_host: one packet per lane over its frame
+// row in LDS (NT * snap_stride bytes of dynamic shared memory, <= 32 KiB), the
+// handle_policy record and flow-group key written directly for ingress_run.  The
+// record keeps GF_PIPE_F_REV_PROXY itself (bit 4 is not among the bits gf_rec.cls
+// carries), so the host side has handle_policy complete the records by
+// read-modify-write (PassArgs::keep_flags) and not write-only.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_host_front(gf_frames fr, const uint32_t *mark, const uint8_t *tc_index,
+                                                   HostDev H, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
+                                                   uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
+                                                   uint8_t *snap_out, unsigned long long *stats) {
+    extern __shared__ uint4 lds_rows[];
+    uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
+    __shared__ uint32_t sl[272];
+    Stats st{sl};
+    if (stats) st.init();
+    const uint32_t S = fr.snap_stride;
+    const uint32_t b0 = blockIdx.x * NT;
+    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
+    const size_t bytes = (size_t)nb * S;
+    {
+        const uint8_t *src = fr.snap + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (H.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
+    }
+    __syncthreads();
+    const uint32_t i = b0 + threadIdx.x;
+    bool scnt = false;                                  // the lane's counter-block entry
+    uint32_t sreason = 0, saction = 0, slen = 0, sab = 0;
+    if (i < fr.n) {
+        const uint32_t len = fr.len[i];
+        const uint32_t cap = S < len ? S : len;
+        Row w{rows + (size_t)threadIdx.x * S, cap};
+        PktHdr h;
+        parse_row(w.p, cap, len, h);
+        const uint32_t et = h.et;
+        gf_pipeline_out o{};
+        uint32_t sec = 0, rev = 0, tun_ip = 0, ifx = 0, lxc = 0, mapped = 0, ndport = 0, skip = 0;
+        uint32_t ab = 24 + 34 + 4;                      // output record, header bytes parsed, mark
+        const uint32_t pid = host_mark_identity(mark ? mark[i] : 0u, skip);   // :425
+        if (H.tcap_in) {                                // from_netdev's send_trace_notify (:433): the frame as received
+            uint8_t *d = H.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
+            const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
+            if (H.vec_copy) {
+                for (uint32_t k = 0; k < cb; k += 16)
+                    *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
+            } else {
+                for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
+            }
+        }
+        const int r = host_program(H, w, h, et, len, pid, sec, rev, tun_ip, ifx, lxc, mapped, ndport, ab);
+        if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
+        if (rev) { o.flags |= GF_PIPE_F_REV_PROXY; skip = 1; }   // :121, :320
+        o.stage = GF_STAGE_HOST;
+        const bool tail = r == ND_TAILCALL;
+        if (tail) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; }
+        else if (r == HO_ENCAP) { o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)H.encap_ifindex; o.daddr4 = tun_ip; }
+        else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
+        else if (r < 0) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }   // send_drop_notify_error (:405-406, :446-447)
+        else o.action = (uint8_t)r;
+        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
+        gf_rec rr;
+        uint32_t key;
+        const uint32_t tci = (tc_index ? tc_index[i] : 0u) | skip;
+        if (tail) {
+            PktHdr h2;
+            parse_row(w.p, cap, len, h2);
+            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx,
+                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr);
+            if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
+                reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
+                reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
+            }
+        } else {
+            // an encap redirect keeps its secctx in the (skipped) record: TRACE_TO_OVERLAY's label
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, r == HO_ENCAP ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr);
+        }
+        rec[i] = rr;
+        keys[i] = key;
+        out[i] = o;
+        sab = ab;                                       // a tail-called packet: handle_policy counts it
+        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
+    }
+    if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
+    if (snap_out) {
+        __syncthreads();
+        uint8_t *dst = snap_out + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (H.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
+    }
+    if (stats) st.flush(stats);
+}
+
 // ---- ingest re-partition (real traffic on N GPUs): the owner rank of each
 // frame is the rank of its flow group, the unordered address pair that the
 // CT of handle_policy sees, i.e. after bpf_lb's translation (stateless, so it
@@ -3594,6 +3855,9 @@ struct EvSrc {
     const uint16_t *lxc_id, *slot_of;   // egress: the sender's program
     uint32_t host_ifindex, encap_ifindex, nd_trace, nd_ifindex;   // nd_trace: 0, or the front program's observation
                                                                   // point | its own final stage << 8
+    // from-host (nd_trace's observation point is TR_FROM_HOST): the per-packet choice of
+    // TRACE_FROM_HOST / FROM_PROXY is made from the batch's mark column (null: all 0)
+    const uint32_t *hmark;
 };
 // One notification: the 8 header words of struct drop_notify / trace_notify and
 // where its captured bytes come from.
@@ -3615,7 +3879,7 @@ __device__ __forceinline__ EvOne ev_trace(uint32_t obs, uint32_t source, uint32_
     return e;
 }
 enum { TR_TO_LXC = 0, TR_TO_PROXY = 1, TR_TO_HOST = 2, TR_TO_STACK = 3, TR_TO_OVERLAY = 4, TR_FROM_LXC = 5,
-       TR_FROM_STACK = 8, TR_FROM_OVERLAY = 9 };
+       TR_FROM_PROXY = 6, TR_FROM_HOST = 7, TR_FROM_STACK = 8, TR_FROM_OVERLAY = 9 };
 // The notifications of packet i in the order the programs send them (k < 0:
 // just count them).  Drops: send_drop_notify / __send_drop_notify (drop.h:47-107)
 // after handle_policy (src_label, SECLABEL, LXC_ID, ifindex), the sender's
@@ -3637,9 +3901,25 @@ __device__ uint32_t ev_list(const EvSrc &E, uint32_t i, int k, EvOne &out) {
     uint32_t n = 0;
     auto put = [&](const EvOne &e) { if ((int)n == k) out = e; n++; };
     if (E.trace) {
-        if (E.kind == 1 && E.nd_trace && (stage == (E.nd_trace >> 8) || stage == GF_STAGE_POLICY))
-            put(ev_trace(E.nd_trace & 0xffu, 0, hash, len, 0, 0, 0, E.nd_ifindex, 0,
-                         E.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN, GF_TRACE_PAYLOAD_LEN));
+        if (E.kind == 1 && E.nd_trace && (stage == (E.nd_trace >> 8) || stage == GF_STAGE_POLICY)) {
+            uint32_t obs = E.nd_trace & 0xffu, src = 0;
+            const uint8_t *cin = E.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
+            if (obs == TR_FROM_HOST) {                      // bpf_netdev.c:423-433: report_identity
+                uint32_t skip;
+                const uint32_t pid = host_mark_identity(E.hmark ? E.hmark[i] : 0u, skip);
+                src = 1u;                                   // HOST_ID
+                if (pid) { obs = TR_FROM_PROXY; src = pid; }
+                put(ev_trace(obs, 0, hash, len, src, 0, 0, E.nd_ifindex, 0, cin, GF_TRACE_PAYLOAD_LEN));
+                if (stage == GF_STAGE_HOST && act == TC_REDIRECT && !(ofl & GF_PIPE_F_ICMP6_TE)) {
+                    // encap_and_redirect's TRACE_TO_OVERLAY (encap.h:67) with the packet's secctx,
+                    // which the front left in the record it packed
+                    put(ev_trace(TR_TO_OVERLAY, 0, hash, len, E.prec[i].src_identity, 0, 0, E.encap_ifindex, 0, fin,
+                                 E.snap_stride));
+                }
+            } else {
+                put(ev_trace(obs, 0, hash, len, 0, 0, 0, E.nd_ifindex, 0, cin, GF_TRACE_PAYLOAD_LEN));
+            }
+        }
         if (E.kind == 2) {
             const uint32_t sl = E.slot_of[E.lxc_id ? E.lxc_id[i] : 0];
             const gf_lxc_dev *sc = sl ? E.cfgs + (sl - 1) : nullptr;
@@ -5779,6 +6059,9 @@ struct PassArgs {                  // what the pipeline / egress callers pass to
                                    // (EvSrc::nd_trace); skb->ingress_ifindex
     const uint8_t *orig;           // egress: the frames as sent
     const uint16_t *lxc_id;        // egress: the senders
+    bool keep_flags;               // from-host: the front's record holds a flag gf_rec.cls does not carry
+                                   // (GF_PIPE_F_REV_PROXY), so handle_policy completes it by read-modify-write
+    const uint32_t *hmark;         // from-host: the mark column (EvSrc::hmark)
 };
 static bool array_traces(const std::shared_ptr<PolicyArray> &a) {
     if (!a) return false;
@@ -6589,7 +6872,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     X.now = now_sec; X.host_ifindex = host_ifindex();
     X.strict = strict;
     X.pout = pout;
-    X.pout_wo = GF_POUT_WO && pout && ta && ta->kind == 1 ? 1u : 0u;
+    X.pout_wo = GF_POUT_WO && pout && ta && ta->kind == 1 && !ta->keep_flags ? 1u : 0u;
     X.pol_wave = ta && ta->kind == 2 ? 1u : 0u;
     X.snap = wsnap; X.snap_stride = ev_stride;
     const gf_node_cfg &node = node_cfg();
@@ -6660,6 +6943,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
             if (ta) {
                 E.nd_trace = ta->nd_trace; E.nd_ifindex = ta->nd_ifindex;
                 E.orig = ta->orig; E.lxc_id = ta->lxc_id;
+                E.hmark = ta->hmark;
                 E.slot_of = (const uint16_t *)a->d_slot_of_lxc.p;
             }
         }
@@ -6973,6 +7257,101 @@ int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf
             hipLaunchKernelGGL(k_ovl_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
                                rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
         return hip_ok(hipGetLastError(), "k_ovl_front");
+    };
+    c2.flow_hash = b->flow_hash;
+    return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
+                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+}
+
+// ---- from-host ----
+int gf_host_load(const gf_host_cfg *cfg) {
+    std::unique_lock<std::shared_mutex> g(prog_lock());
+    if (!cfg) return -EFAULT;
+    auto p = std::make_shared<ProgHost>();
+    p->cfg = *cfg;
+    auto m = get_map(cfg->netdev.lxc_map);
+    if (!m) return -EBADF;
+    if (m->ksz != 20 || m->vsz != 112 || m->is_lpm()) return -EINVAL;
+    p->lxc = m;
+    auto a = get_obj(cfg->policy_array);
+    if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
+    p->policy = std::static_pointer_cast<PolicyArray>(a);
+    return new_handle(p);
+}
+
+int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipeline_out *out,
+                     uint8_t *snap_out, void *stream) {
+    std::shared_lock<std::shared_mutex> g(prog_lock());
+    auto o = get_obj(host);
+    if (!o || o->kind != ObjKind::ProgHost) return -EBADF;
+    auto p = std::static_pointer_cast<ProgHost>(o);
+    if (!b) return -EFAULT;
+    const gf_frames &fr = b->frames;
+    if (fr.n == 0) return 0;
+    if (!fr.snap || !fr.len || !out) return -EFAULT;
+    if (fr.snap_stride < 14 || fr.snap_stride > 256) return -EINVAL;   // a header snap, staged in LDS
+    if (fr.n > (1u << 30)) return -E2BIG;
+    hipStream_t s = (hipStream_t)stream;
+    HostMarks hm;
+    CtxScope cx(s);
+    std::lock_guard<std::mutex> ag(p->policy->mu);
+    // cilium_proxy{4,6}, the tunnel map and the node's cilium_lxc are among the array's
+    // maps: the front reads them under the locks ingress_run writes them under
+    MapLocks L;
+    L.add(p->lxc);
+    lock_array_maps(L, p->policy);
+    L.lock();
+    CallOrder co(s, L, p->policy.get());
+    int r;
+    const uint32_t n = fr.n;
+    HostDev H{};
+    auto px4 = proxy_map(4), px6 = proxy_map(6), tun = node_map(2);
+    if ((r = push_map(p->lxc, s)) || (r = push_map(px4, s)) || (r = push_map(px6, s)) || (r = push_map(tun, s))) return r;
+    H.lxc = p->lxc->hdesc();
+    if (getenv("GF_XDP_NOSETS") || p->lxc->addr_set(20, 8192, s, &H.lxset, &H.lxbits, &H.lxzero)) H.lxset = nullptr;
+    if (px4) H.px4 = px4->hdesc();
+    if (px6) H.px6 = px6->hdesc();
+    const gf_node_cfg &node = node_cfg();
+    H.encap_ifindex = node.encap_ifindex;
+    if (tun && node.encap_ifindex) {
+        H.tunnel = tun->hdesc();
+        if (getenv("GF_XDP_NOSETS") || tun->addr_set(20, 8192, s, &H.tnset, &H.tnbits, &H.tnzero)) H.tnset = nullptr;
+    }
+    H.cluster_range = node.ipv4_cluster_range; H.cluster_mask = node.ipv4_cluster_mask; H.ipv4_mask = node.ipv4_mask;
+    memcpy(H.node6, node.router_ip6, 12);
+    H.flags = p->cfg.netdev.flags; H.fixed_secctx = p->cfg.netdev.fixed_secctx;
+    memcpy(H.router6, p->cfg.netdev.router_ip6, 8);
+    memcpy(H.net_mac, p->cfg.cilium_net_mac, 6);
+    // LDS staging as k_pipe_front: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B (<= 32 KiB)
+    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
+    const size_t lds = (size_t)nt * fr.snap_stride;
+    PipeWs &w = pipe_ws();
+    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
+    if ((r = grow(w.s6, (size_t)n * 32))) return r;    // saddr6 | daddr6 per packet (IngCtx::a6_stride 32)
+    H.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
+    PassArgs ta{};
+    ta.kind = 1;                                       // records completed as the pipeline's
+    ta.keep_flags = true;
+    ta.nd_trace = (p->cfg.netdev.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_HOST | (GF_STAGE_HOST << 8)) : 0u;
+    ta.nd_ifindex = p->cfg.netdev.ingress_ifindex;
+    ta.hmark = b->mark;
+    ta.on = event_ring().records && (ta.nd_trace || array_traces(p->policy));
+    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
+    if (ta.on && ta.nd_trace) H.tcap_in = (uint8_t *)trace_ws().in.p;
+    unsigned long long *sink = (unsigned long long *)stats_sink();
+    const uint32_t grid = (n + nt - 1) / nt;         // one NT-frame tile per block
+    gf_pkt_cols c2{};
+    c2.n = n;
+    c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
+    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
+        ProfScope ps("k_host_front", s);
+        if (nt == 256)
+            hipLaunchKernelGGL(k_host_front<256>, dim3(grid), dim3(256), lds, s, fr, b->mark, b->tc_index, H, slot_of,
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+        else
+            hipLaunchKernelGGL(k_host_front<128>, dim3(grid), dim3(128), lds, s, fr, b->mark, b->tc_index, H, slot_of,
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+        return hip_ok(hipGetLastError(), "k_host_front");
     };
     c2.flow_hash = b->flow_hash;
     return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,

@@ -17,7 +17,7 @@ import numpy as np
 from . import bpf
 from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
-                   gf_overlay_batch)
+                   gf_overlay_batch, gf_host_cfg, gf_host_batch)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
                    ("rev_nat", "<u2"), ("new_daddr4", "<u4")])
@@ -98,6 +98,7 @@ class DeviceBatch:
         self.tc_index = t(pk.tc_index, np.uint8)
         self.flow_hash = t(pk.flow_hash, np.uint32)
         self.tunnel_id = t(getattr(pk, "tunnel_id", None), np.uint32)   # bpf_tunnel_key.tunnel_id (from-overlay)
+        self.mark = t(getattr(pk, "mark", None), np.uint32)             # skb->mark (from-host)
         n = self.n
         e = lambda dt, *shape: torch.empty((n,) + shape, dtype=dt, device=device)
         self.ethertype = e(torch.int16)
@@ -210,6 +211,16 @@ class Datapath:
             ocfg = gf_overlay_cfg(h(ov["lxc_map"]), ov.get("flags", 0), ov.get("ingress_ifindex", 0), self.policy_array)
             self.ovl = _check(lib.gf_overlay_load(C.byref(ocfg)), "gf_overlay_load")
 
+        # the program on cilium_host (bpf_netdev.c with FROM_HOST), sc.host = {lxc_map, flags, fixed_secctx,
+        # router_ip6, ingress_ifindex, cilium_net_mac}
+        self.host = None
+        if getattr(sc, "host", None) and self.policy_array:
+            ho = sc.host
+            ncfg = gf_netdev_cfg(h(ho["lxc_map"]), ho.get("flags", 0), ho.get("fixed_secctx", 0),
+                                 (C.c_uint8 * 16)(*ho.get("router_ip6", bytes(16))), ho.get("ingress_ifindex", 0))
+            hcfg = gf_host_cfg(ncfg, (C.c_uint8 * 6)(*ho.get("cilium_net_mac", bytes(6))), self.policy_array)
+            self.host = _check(lib.gf_host_load(C.byref(hcfg)), "gf_host_load")
+
     # ---- classify calls -------------------------------------------------
     def xdp(self, b):
         torch = _torch()
@@ -278,6 +289,20 @@ class Datapath:
                "gf_overlay_classify")
         return out, snap
 
+    def from_host(self, b, now, out=None, snap_out=True):
+        """from-host (cilium_host) over the batch's frames and marks (+ handle_policy of the
+        local deliveries): returns (records [n,24] u8, rewritten snaps or None)."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty((b.n, 24), dtype=torch.uint8, device=b.device)
+        snap = torch.empty_like(b.frames) if snap_out else None
+        stride = b.frames.shape[1] if b.n else 64
+        hb = gf_host_batch(gf_frames(b.n, stride, _ptr(b.frames), _ptr(b.len)), _ptr(b.mark), _ptr(b.tc_index),
+                           _ptr(b.flow_hash))
+        _check(lib.gf_host_classify(self.host, C.byref(hb), now, _ptr(out), _ptr(snap), _stream()),
+               "gf_host_classify")
+        return out, snap
+
     def egress(self, b, now, out=None, snap_out=True):
         """The from-container program over the batch's frames (+ handle_policy of the
         local deliveries): returns (records [n,24] u8, rewritten snaps or None)."""
@@ -303,13 +328,13 @@ class Datapath:
     def close(self):
         """Close the program objects, then the maps (a program holds its maps, so
         their device tables are released once both are closed)."""
-        progs = [self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
+        progs = [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
         for h in [h for h in progs if h] + list(self.fd.values()):
             try:
                 bpf.ObjClose(h)
             except OSError:
                 pass
-        self.ovl = self.pipe = self.policy_array = self.lb_prog = self.xdp_prog = None
+        self.host = self.ovl = self.pipe = self.policy_array = self.lb_prog = self.xdp_prog = None
         self.lxc_progs = []
         self.fd = {}
 

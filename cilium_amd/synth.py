@@ -50,6 +50,7 @@ class Packets:
     tc_index: np.ndarray = None
     flow_hash: np.ndarray = None
     tunnel_id: np.ndarray = None  # bpf_tunnel_key.tunnel_id per frame (from-overlay batches)
+    mark: np.ndarray = None       # skb->mark per frame (from-host batches; None = all 0)
 
     @property
     def n(self):
@@ -58,7 +59,7 @@ class Packets:
     def slice(self, a, b):
         f = lambda x: None if x is None else x[a:b]
         return Packets(self.frames[a:b], self.lens[a:b], f(self.src_identity), f(self.ifindex), f(self.lxc_id),
-                       f(self.tc_index), f(self.flow_hash), f(self.tunnel_id))
+                       f(self.tc_index), f(self.flow_hash), f(self.tunnel_id), f(self.mark))
 
 
 @dataclass
@@ -75,6 +76,8 @@ class Scenario:
     now: int = 1000
     meta: dict = field(default_factory=dict)
     overlay: dict = None         # bpf_overlay config (gf_overlay_cfg): {'lxc_map','flags','ingress_ifindex'}
+    host: dict = None            # bpf_netdev with FROM_HOST (gf_host_cfg): {'lxc_map','flags' (NETDEV_*),
+                                 # 'fixed_secctx','router_ip6','ingress_ifindex','cilium_net_mac'}
 
     def add_map(self, spec):
         self.maps[spec.name] = spec
@@ -1023,6 +1026,70 @@ def overlay_fuzz(seed=3, n_packets=20000, n_batches=3, strangers=0.1, to_host=0.
         sc.batches[k] = Packets(f, pk.lens, pk.src_identity, pk.ifindex, pk.lxc_id, pk.tc_index, pk.flow_hash, tid)
     assert sc.host_ifindex
     sc.overlay = {"lxc_map": "cilium_lxc", "flags": 0, "ingress_ifindex": 9}
+    return sc
+
+
+def host_fuzz(seed=3, n_packets=20000, n_batches=3, reverse=0.3, remote=0.15, encap_ifindex=7, **kw):
+    """pipeline_fuzz's frames as cilium_host sees them (bpf_netdev.c with FROM_HOST): a mark
+    column (a quarter each from the ingress and the egress proxy with the batch's identity
+    column, a few 0xFEA marks without an identity and near-miss magics, the rest 0);
+    cilium_proxy4 / 6 hold, from the start, the reverse key of `reverse` of each batch's
+    TCP / UDP frames (random original address and port); `remote` of the IP frames are
+    readdressed into the cluster range outside cilium_lxc, half of the IPv4 /24s and the one
+    IPv6 /96 with a tunnel endpoint (ENCAP_IFINDEX = encap_ifindex, 0 = undefined)."""
+    sc = pipeline_fuzz(seed, n_packets, n_batches, **kw)
+    sc.name = f"host{seed}"
+    rng = np.random.default_rng(seed ^ 0x4057)
+    router = sc.netdev["router_ip6"]
+    k4, v4, k6, v6 = [], [], [], []
+    for k, pk in enumerate(sc.batches):
+        f, m = pk.frames, pk.n
+        et = (f[:, 12].astype(np.uint32) << 8) | f[:, 13]
+        is4, is6 = (et == 0x0800) & (pk.lens >= 34), (et == 0x86DD) & (pk.lens >= 54)
+        far = rng.random(m) < remote
+        r4 = np.nonzero(far & is4)[0]
+        f[r4, 30:32] = (10, 77)
+        f[r4, 32:34] = rng.integers(0, 16, (len(r4), 2))
+        r6 = np.nonzero(far & is6)[0]
+        f[r6, 38:50] = np.frombuffer(router[:12], np.uint8)
+        f[r6, 50:54] = rng.integers(0, 256, (len(r6), 4))
+        # reverse keys: {saddr = daddr, dport = sport, sport = dport, nexthdr} of frames of this batch
+        l4 = np.where(is4, 14 + (f[:, 14] & 0xf).astype(np.int64) * 4, 54)
+        nh = np.where(is4, f[:, 23], f[:, 20])
+        pick = (rng.random(m) < reverse) & (is4 | is6) & np.isin(nh, (6, 17)) & (l4 + 4 <= np.minimum(pk.lens, f.shape[1]))
+        for i in np.nonzero(pick)[0]:
+            ports = bytes(f[i, l4[i]:l4[i] + 4])
+            val_tail = bytes(rng.integers(1, 256, 2).astype(np.uint8)) + bytes(2) + \
+                int(pk.src_identity[i]).to_bytes(4, "little") + int(sc.now + 700).to_bytes(4, "little")
+            if is4[i]:
+                k4.append(bytes(f[i, 30:34]) + ports + bytes([nh[i], 0]))
+                v4.append(bytes(rng.integers(1, 255, 4).astype(np.uint8)) + val_tail)
+            else:
+                k6.append(bytes(f[i, 38:54]) + ports + bytes([nh[i], 0]))
+                v6.append(bytes(rng.integers(1, 255, 16).astype(np.uint8)) + val_tail)
+        ident = pk.src_identity.astype(np.uint32) & 0xffff
+        u = rng.random(m)
+        mark = np.zeros(m, np.uint32)
+        mark[u < 0.25] = 0xFEA | (ident[u < 0.25] << 16)
+        sel = (u >= 0.25) & (u < 0.5)
+        mark[sel] = 0xFEB | (ident[sel] << 16)
+        mark[(u >= 0.5) & (u < 0.52)] = 0xFEA
+        sel = (u >= 0.52) & (u < 0.55)
+        mark[sel] = 0xFEC | (ident[sel] << 16)
+        sc.batches[k] = Packets(f, pk.lens, pk.src_identity, pk.ifindex, pk.lxc_id, pk.tc_index, pk.flow_hash, None, mark)
+    for name, ks, vs, ksz, vsz in (("cilium_proxy4", k4, v4, 10, 16), ("cilium_proxy6", k6, v6, 22, 28)):
+        if ks:
+            d = dict(zip(ks, vs))
+            sc.maps[name].keys = np.frombuffer(b"".join(d.keys()), np.uint8).reshape(-1, ksz).copy()
+            sc.maps[name].vals = np.frombuffer(b"".join(d.values()), np.uint8).reshape(-1, vsz).copy()
+    # the tunnel map: every second 10.77.x.0/24 and the router's /96
+    t4 = np.array([ip4(f"10.77.{a}.0") for a in range(0, 16, 2)], np.uint32)
+    tk = np.concatenate([endpoint_keys4(t4), endpoint_keys6(np.frombuffer(router[:12] + bytes(4), np.uint8)[None, :])])
+    tv = endpoint_keys4((ip4("192.168.9.1") + np.arange(len(tk))).astype(np.uint32))
+    sc.add_map(MapSpec("cilium_tunnel_map", HASH, 20, 20, 1024, 0, tk, tv))
+    sc.node = dict(sc.node, encap_ifindex=encap_ifindex, tunnel_map="cilium_tunnel_map", router_ip6=router,
+                   ipv4_cluster_range=0x00004d0a, ipv4_cluster_mask=0x0000ffff, ipv4_mask=0x00ffffff)   # raw be32
+    sc.host = dict(sc.netdev, ingress_ifindex=5, cilium_net_mac=bytes([0x02, 0xc1, 0x11, 0x0e, 0x70, 0x01]))
     return sc
 
 

@@ -35,6 +35,8 @@
  *     gf_pipeline_classify       <- bpf_xdp -> bpf_lb -> bpf_netdev -> cilium_policy tail call
  *     gf_overlay_classify        <- from_overlay (tunnel receive) bpf/bpf_overlay.c:38-200 -> cilium_policy
  *                                   tail call (VXLAN; no DROP_NO_TUNNEL_KEY, no Geneve options)
+ *     gf_host_classify           <- from_netdev with FROM_HOST (cilium_host) bpf/bpf_netdev.c:50-468 ->
+ *                                   cilium_policy tail call (the proxy return path; no HANDLE_NS)
  *     gf_parse_frames            <- the skb_load_bytes()/revalidate_data() header
  *                                   accesses of those programs (bpf/lib/common.h:67-87,
  *                                   bpf/lib/ipv4.h:45-48, bpf/lib/ipv6.h:61-98)
@@ -535,6 +537,79 @@ typedef struct gf_overlay_batch {
 int gf_overlay_classify(int ovl, const gf_overlay_batch *batch, uint32_t now_sec,
                         gf_pipeline_out *out, uint8_t *snap_out, void *stream);
 
+/* ---- from-host: the program on cilium_host (bpf/bpf_netdev.c:50-468 compiled with
+ * -DFROM_HOST, bpf/init.sh:359-360) ----
+ * Everything the host sends to pods takes this program: health probes, kubelet, host
+ * to remote pods over the tunnel, and the L7 proxy's return path, which is where the
+ * cilium_proxy{4,6} entries handle_policy and the container egress path write are
+ * read back.  FROM_HOST and ENABLE_IPV4 defined, HANDLE_NS undefined (no responders),
+ * FIXED_SRC_SECCTX per gf_netdev_cfg, ENCAP_IFINDEX defined iff
+ * gf_node_cfg.encap_ifindex != 0.  Per frame, in the reference's order:
+ *   from_netdev (:414-468): handle_identity_from_proxy (:128-145) on mark:
+ *           mark & 0xFFF == 0xFEA (ingress proxy): proxy_identity = mark >> 16 and
+ *           tc_index |= TC_INDEX_F_SKIP_PROXY; == 0xFEB (egress proxy): proxy_identity
+ *           only; else neither.  The reset of skb->mark to 0 has no output column.
+ *           Ethertype other than 0x0800 / 0x86DD: TC_ACT_OK, frame untouched.
+ *   handle_ipv4 (:328-396) / handle_ipv6 (:163-246): len < 34 / 54 DROP_INVALID;
+ *           secctx = FIXED_SRC_SECCTX, else WORLD_ID (v4) / derive_sec_ctx (v6),
+ *           overridden by a non-zero proxy_identity;
+ *           reverse_proxy (:264-325) / reverse_proxy6 (:67-124), TCP and UDP only (v6:
+ *           by ip6->nexthdr, so a frame with an extension header is ignored): the 4 port
+ *           bytes not loadable DROP_CT_INVALID_HDR; key {saddr = daddr, dport = sport,
+ *           sport = dport, nexthdr} in cilium_proxy4 / 6 (lifetime is not consulted); on
+ *           a hit l4_modify_port of the source port (its checksum field outside the frame:
+ *           DROP_WRITE_ERROR), the source address, the IPv4 header checksum, the L4
+ *           checksum (BPF_F_PSEUDO_HDR; UDP with BPF_F_MARK_MANGLED_0), tc_index |=
+ *           TC_INDEX_F_SKIP_PROXY, and GF_PIPE_F_REV_PROXY in the record;
+ *           rewrite_dmac_to_host (:148-160): dmac = CILIUM_NET_MAC, hit or miss;
+ *           the endpoint lookup in cilium_lxc: ENDPOINT_F_HOST TC_ACT_OK; a local
+ *           endpoint ipv{4,6}_local_delivery with secctx (TTL <= 1 DROP_INVALID, hop
+ *           limit <= 1 GF_PIPE_F_ICMP6_TE) and the cilium_policy tail call; no endpoint,
+ *           ENCAP_IFINDEX defined and the destination in the cluster range (v4:
+ *           ipv4_cluster_mask / range; v6: the /96 of gf_node_cfg.router_ip6):
+ *           encap_and_redirect (lib/encap.h:30-70) with the tunnel_map key daddr &
+ *           ipv4_mask (v6: daddr/96), a miss falling through; otherwise TC_ACT_OK.
+ * Errors end in send_drop_notify_error(skb, ret, TC_ACT_SHOT).
+ * Records are gf_pipeline_out: stage GF_STAGE_HOST for the verdicts the program itself
+ * ends; an encap redirect has action REDIRECT, ifindex_lo = ENCAP_IFINDEX and, reusing
+ * the field lb4_xlate's address has in the pipeline, daddr4 = the tunnel endpoint
+ * (bpf_tunnel_key.remote_ipv4, host byte order as gf_egress_out.tunnel_ip).  Tail-called
+ * packets get stage GF_STAGE_POLICY, completed by handle_policy as for the overlay.
+ * GF_PIPE_F_REV_PROXY lies outside the three flag bits the pipeline's front hands
+ * handle_policy in gf_rec.cls; it is carried in the record itself, which handle_policy
+ * completes by read-modify-write for this entry point.
+ * Ordering: the front reads cilium_proxy4 / 6 as they stood when the call began; a
+ * reverse lookup never sees an entry handle_policy creates later in the same call.  The
+ * call holds the maps' locks from before the front's reads to after handle_policy's
+ * writes.  The proxy maps, tunnel map, cluster values and encap_ifindex come from
+ * gf_node_config.  With an event ring set, drops are recorded as the pipeline records
+ * them and GF_NETDEV_F_TRACE_NOTIFY makes each packet's first record TRACE_FROM_PROXY
+ * (subtype 6, src_label = proxy_identity) when proxy_identity != 0, else TRACE_FROM_HOST
+ * (subtype 7, src_label = HOST_ID); ifindex = ingress_ifindex, the frame as received
+ * (:423-433).  A mark of 0x00000FEA sets the skip bit but leaves proxy_identity 0, so it
+ * traces as FROM_HOST.  An encap redirect adds TRACE_TO_OVERLAY (src_label = secctx,
+ * ifindex = ENCAP_IFINDEX). */
+#define GF_STAGE_HOST 7            /* the from-host verdict is final */
+#define GF_PIPE_F_REV_PROXY 0x10   /* gf_pipeline_out.flags: reverse_proxy / reverse_proxy6 translated the source */
+typedef struct gf_host_cfg {
+    gf_netdev_cfg netdev;          /* lxc_map, GF_NETDEV_F_FIXED_SECCTX / _TRACE_NOTIFY, fixed_secctx,
+                                      router_ip6 (derive_sec_ctx), ingress_ifindex (cilium_host's) */
+    uint8_t cilium_net_mac[6];     /* CILIUM_NET_MAC (rewrite_dmac_to_host) */
+    int policy_array;              /* cilium_policy prog array */
+} gf_host_cfg;
+int gf_host_load(const gf_host_cfg *cfg);
+typedef struct gf_host_batch {
+    gf_frames frames;              /* DEVICE frames, snap_stride 14..256 as the pipeline */
+    const uint32_t *mark;          /* DEVICE skb->mark per frame; may be NULL (all 0) */
+    const uint8_t  *tc_index;      /* DEVICE, may be NULL */
+    const uint32_t *flow_hash;     /* DEVICE, may be NULL (the event records' hash) */
+} gf_host_batch;
+/* snap_out (n * snap_stride, may be NULL): every frame as rewritten before
+ * handle_policy.  -EBADF, -EFAULT (a NULL batch, frame pointer or out), -EINVAL
+ * (snap_stride < 14 or > 256), -E2BIG; n == 0 returns 0. */
+int gf_host_classify(int host, const gf_host_batch *batch, uint32_t now_sec,
+                     gf_pipeline_out *out, uint8_t *snap_out, void *stream);
+
 /* ---- ingest re-partition for N GPUs (real traffic) ----
  * owner[i] = the rank owning packet i's flow group: the unordered address pair
  * handle_policy's conntrack sees (after bpf_lb's translation, which is
@@ -603,6 +678,7 @@ int gf_ct_evict_log(int map, gf_ct_evict_rec *out, uint32_t max);
  * ring (type CILIUM_NOTIFY_TRACE=4, subtype = observation point TRACE_TO_LXC 0,
  * TO_PROXY 1, TO_HOST 2, TO_STACK 3, TO_OVERLAY 4, FROM_LXC 5, FROM_STACK 8, FROM_OVERLAY 9
  * (gf_overlay_classify with GF_OVERLAY_F_TRACE_NOTIFY);
+ * FROM_PROXY 6 / FROM_HOST 7 (gf_host_classify with GF_NETDEV_F_TRACE_NOTIFY);
  * source = EVENT_SOURCE, hash, len_orig, len_cap, src_label, dst_label, dst_id
  * (u16), reason (the CT result that forwarded it), pad, ifindex — the layout
  * pkg/monitor/datapath_trace.go TraceNotify decodes), followed by the first

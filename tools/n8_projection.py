@@ -67,7 +67,8 @@ def main():
             c4_fixed = max(t_c4 - c4_oracle_n1, 0.0)
             c4_pk8 = (4 + max(4, K // 2)) * per_step / div4
             c4_leg = c4_fixed + c4_pk8 / (rate_thread / 2 * T)
-        legs = {"config2_s": round(c2, 1), "config2_parity_div": div2, "config4_owned_s": c4_leg and round(c4_leg, 1),
+        # three decimals: a rehearsal-sized run (tables in under 50 ms) must not round to 0.0
+        legs = {"config2_s": round(c2, 3), "config2_parity_div": div2, "config4_owned_s": c4_leg and round(c4_leg, 1),
                 "config4_exchange_s": c4_leg and round(c4_leg * 1.1, 1), "config4_parity_div": div4}
         total = a.startup_s + (c2 + (2.1 * c4_leg if c4_leg else 0.0)) * a.contention
         out["projection"][f"T{T}"] = dict(legs, total_s=round(total, 1), within_390s=total <= 390)
