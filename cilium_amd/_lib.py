@@ -189,6 +189,8 @@ _sig("gf_overlay_classify", C.c_int, C.c_int, C.POINTER(gf_overlay_batch), C.c_u
 _sig("gf_host_load", C.c_int, C.POINTER(gf_host_cfg))
 _sig("gf_host_classify", C.c_int, C.c_int, C.POINTER(gf_host_batch), C.c_uint32, VP, VP, VP)
 _sig("gf_ct_gc", C.c_int, C.c_int, C.c_uint32, VP)
+_sig("gf_proxy_gc", C.c_int, C.c_int, C.c_uint32, VP)
+_sig("gf_proxy_cleanup_port", C.c_int, C.c_int, C.c_uint16, VP)
 
 
 class gf_ct_evict_rec(C.Structure):
@@ -219,7 +221,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

@@ -3274,6 +3274,71 @@ __global__ __launch_bounds__(BLOCK) void k_gc_clusters(gf_htab_desc d, uint32_t 
     if (tombs) atomicAdd(&res[1], (unsigned long long)tombs);
 }
 
+// ---- cilium_proxy{4,6} sweeps (gf_proxy_gc / gf_proxy_cleanup_port; pkg/maps/proxymap:
+// gc / gc6, cleanupIPv{4,6}Redirects).  The same two-step sweep over the proxy maps'
+// own layout and hash (GF_HASH_PLAIN, the slot geometry of hdesc()): k_gc_starts marks
+// the cluster starts, k_px_gc walks each cluster with one lane.  The predicate is a
+// launch argument: by lifetime (the last u32 of proxy{4,6}_tbl_value, strictly below
+// the cutoff) or by port (key.dport == arg as stored, and key.nexthdr == 6).
+enum { GF_PXGC_LIFETIME = 0, GF_PXGC_PORT = 1 };
+struct PxGcPred {
+    uint32_t mode;              // GF_PXGC_*
+    uint32_t arg;               // the cutoff (seconds) or the raw be16 port
+    uint32_t off;               // value offset of lifetime / key offset of dport
+    uint32_t nh_off;            // key offset of nexthdr (port mode)
+};
+struct PxGcDev {                // per call context, device memory
+    GcCut on;                   // k_gc_starts' switch (active = 1)
+    unsigned long long res[2];  // entries deleted, tombstones cleared
+};
+__device__ __forceinline__ bool px_gc_kill(const gf_htab_desc &d, uint64_t j, const PxGcPred &P) {
+    if (P.mode == GF_PXGC_LIFETIME) return *reinterpret_cast<const uint32_t *>(ht_val(d, j) + P.off) < P.arg;
+    const uint8_t *k = d.slots + j * d.slot_size;
+    return *reinterpret_cast<const uint16_t *>(k + P.off) == P.arg && k[P.nh_off] == 6;
+}
+__global__ __launch_bounds__(BLOCK) void k_px_gc(gf_htab_desc d, PxGcPred P, const uint32_t *bits, unsigned long long *res) {
+    const uint64_t nw = (d.mask + 1 + 31) / 32;
+    uint32_t dead = 0, tombs = 0;
+    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t m = bits[w];
+        while (m) {
+            const int k = __builtin_ctz(m);
+            m &= m - 1;
+            uint64_t j = w * 32 + k;
+            // as in k_gc_clusters: nothing moves until this walk has emptied a slot of the
+            // cluster; n bounds the walk by the table (a cluster ends at an EMPTY slot)
+            bool hole = false;
+            for (uint64_t n = 0; n <= d.mask; n++, j = (j + 1) & d.mask) {
+                uint8_t *sl = d.slots + j * d.slot_size;
+                const uint32_t st = sl[d.ksz];
+                if (st == GF_SLOT_EMPTY) break;
+                if (st == GF_SLOT_TOMB || st == GF_SLOT_FREE) {
+                    sl[d.ksz] = GF_SLOT_EMPTY;
+                    tombs++;
+                    hole = true;
+                } else if (px_gc_kill(d, j, P)) {
+                    sl[d.ksz] = GF_SLOT_EMPTY;
+                    dead++;
+                    hole = true;
+                } else if (hole) {
+                    uint32_t kw[6];                             // 22 B at most (gf_proxy_* checks the sizes)
+                    for (uint32_t q = 0; q < 6; q++) kw[q] = 0;
+                    for (uint32_t q = 0; q < d.ksz; q += 4) {   // slots are 16-B aligned
+                        const uint32_t x = *reinterpret_cast<const uint32_t *>(sl + q);
+                        kw[q >> 2] = d.ksz - q >= 4 ? x : (x & ((1u << (8 * (d.ksz - q))) - 1u));
+                    }
+                    const uint64_t home = gf_home_slot(gf_key_hash(kw, d.ksz, GF_HASH_PLAIN), d.mask, d.slot_size);
+                    for (uint64_t p = home; p != j; p = (p + 1) & d.mask) {
+                        if (d.slots[p * d.slot_size + d.ksz] == GF_SLOT_EMPTY) { gc_move(d, j, p, 0u); break; }
+                    }
+                }
+            }
+        }
+    }
+    if (dead) atomicAdd(&res[0], (unsigned long long)dead);
+    if (tombs) atomicAdd(&res[1], (unsigned long long)tombs);
+}
+
 // ---- LRU stand-in (CT maps are BPF_MAP_TYPE_LRU_HASH, bpf/bpf_lxc.c:53-75;
 // ctmap.go:38-39).  The kernel never fails an LRU insert: it evicts from per-CPU
 // LRU lists, taking entries off the tail of an inactive list it keeps about as
@@ -7472,6 +7537,87 @@ int gf_ct_gc(int map, uint32_t filter_time, void *stream) {
     m->st_floor = m->lru_seq;
     m->device_modified();
     return (int)std::min<unsigned long long>(r[0], 0x7fffffff);
+}
+
+// ---- proxy map GC / redirect-close cleanup ----
+// Both states of a map, as gf_ct_gc: on the host shadow while it is authoritative (no
+// launch, no device needed), else a sweep of the HBM replica.  After the sweep the
+// device count drops by the entries deleted and the host's bound of it (dev_count_hi,
+// which px_log_apply only ever raises) is that exact count, so the next proxy log is
+// applied in parallel again whenever count + log <= max_entries.
+static int px_gc(int map, const PxGcPred &pred_of_v4, const PxGcPred &pred_of_v6, void *stream) {
+    std::shared_lock<std::shared_mutex> g(prog_lock());
+    auto m = get_map(map);
+    if (!m) return -EBADF;
+    const bool v4 = m->ksz == 10 && m->vsz == 16, v6 = m->ksz == 22 && m->vsz == 28;
+    if (m->is_lpm() || (!v4 && !v6)) return -EINVAL;
+    const PxGcPred P = v4 ? pred_of_v4 : pred_of_v6;
+    hipStream_t s = (hipStream_t)stream;
+    CtxScope cx(s);
+    std::lock_guard<std::recursive_mutex> mg(m->mu);
+    CallOrder co(s, std::vector<OrderPt *>{&m->ord});
+    if (m->host_valid || !m->dev_valid || !m->d_slots.p) {
+        if (m->ht.slots.empty()) return 0;              // never materialised: no entries
+        uint64_t dead = 0;
+        std::vector<std::string> keys;
+        uint8_t v[28];
+        for (uint64_t i = 0; i < m->ht.nslots; i++) {
+            if (m->ht.state(i) != GF_SLOT_FULL) continue;
+            const uint8_t *k = m->ht.key(i);
+            bool kill;
+            if (P.mode == GF_PXGC_LIFETIME) {
+                m->ht.get_val(i, v);
+                uint32_t lt;
+                memcpy(&lt, v + P.off, 4);
+                kill = lt < P.arg;
+            } else {
+                uint16_t dp;
+                memcpy(&dp, k + P.off, 2);
+                kill = dp == P.arg && k[P.nh_off] == 6;
+            }
+            if (kill) keys.emplace_back((const char *)k, m->ksz);
+        }
+        for (auto &k : keys) if (m->erase((const uint8_t *)k.data()) == 0) dead++;
+        return (int)std::min<uint64_t>(dead, 0x7fffffff);
+    }
+    struct PxGcWs { DevBuf st; };
+    static const char tag = 0;
+    DevBuf &st = cur_ctx().get<PxGcWs>(&tag).st;
+    if (!st.p && st.ensure(sizeof(PxGcDev))) return -ENOMEM;
+    const size_t nw = (m->ht.nslots + 31) / 32;
+    if (m->d_gcbits.bytes < nw * 4 && m->d_gcbits.ensure(nw * 4)) return -ENOMEM;
+    PxGcDev *D = (PxGcDev *)st.p;
+    uint32_t *bits = (uint32_t *)m->d_gcbits.p;
+    PxGcDev init{};
+    init.on.active = 1u;
+    if (hip_ok(hipMemcpyAsync(D, &init, sizeof init, hipMemcpyHostToDevice, s), "proxy gc init")) return -EIO;
+    {
+        ProfScope ps("k_px_gc", s);
+        const gf_htab_desc d = m->hdesc();
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((nw + BLOCK - 1) / BLOCK, 65535u * 8);
+        hipLaunchKernelGGL(k_gc_starts, dim3(grid), dim3(BLOCK), 0, s, d, bits, (const GcCut *)&D->on);
+        hipLaunchKernelGGL(k_px_gc, dim3(grid), dim3(BLOCK), 0, s, d, P, (const uint32_t *)bits, D->res);
+    }
+    if (hip_ok(hipGetLastError(), "k_px_gc")) return -EIO;
+    unsigned long long r[2] = {0, 0};
+    if (hip_ok(hipMemcpyAsync(r, D->res, 16, hipMemcpyDeviceToHost, s), "proxy gc result") ||
+        hip_ok(hipStreamSynchronize(s), "proxy gc sync"))
+        return -EIO;
+    uint32_t cnt = 0;
+    int rr;
+    if ((rr = m->dev_count(cnt))) return rr;
+    cnt = cnt >= r[0] ? cnt - (uint32_t)r[0] : 0u;
+    if ((rr = m->dev_set_count(cnt))) return rr;        // the device count and dev_count_hi, both exact
+    m->device_modified();
+    return (int)std::min<unsigned long long>(r[0], 0x7fffffff);
+}
+
+int gf_proxy_gc(int map, uint32_t filter_time, void *stream) {
+    return px_gc(map, PxGcPred{GF_PXGC_LIFETIME, filter_time, 12u, 0u}, PxGcPred{GF_PXGC_LIFETIME, filter_time, 24u, 0u}, stream);
+}
+
+int gf_proxy_cleanup_port(int map, uint16_t dport, void *stream) {
+    return px_gc(map, PxGcPred{GF_PXGC_PORT, dport, 4u, 8u}, PxGcPred{GF_PXGC_PORT, dport, 16u, 20u}, stream);
 }
 
 #if GF_WRSTATS

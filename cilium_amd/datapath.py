@@ -316,6 +316,16 @@ class Datapath:
                "gf_lxc_egress_classify")
         return out, snap
 
+    # ---- proxy map sweeps (pkg/maps/proxymap: GC / Flush, CleanupOnRedirectClose) ----
+    def proxy_gc(self, name, filter_time):
+        """gf_proxy_gc on the current stream: deletes lifetime < filter_time, returns the count."""
+        return _check(lib.gf_proxy_gc(self.fd[name], filter_time & 0xFFFFFFFF, _stream()), "gf_proxy_gc")
+
+    def proxy_cleanup_port(self, name, port):
+        """gf_proxy_cleanup_port on the current stream: deletes the TCP entries whose dport is
+        `port` (host order here, stored in network order), returns the count."""
+        return _check(lib.gf_proxy_cleanup_port(self.fd[name], _be16(port), _stream()), "gf_proxy_cleanup_port")
+
     # ---- map readback ----------------------------------------------------
     def dump_map(self, name):
         m = self.sc.maps[name]

@@ -630,6 +630,25 @@ int gf_pipeline_partition(int pipe, const gf_pipe_batch *batch, uint32_t self_ra
  * host shadow.  Synchronous on `stream`. */
 int gf_ct_gc(int map, uint32_t filter_time, void *stream);
 
+/* ---- proxy map garbage collection and redirect-close cleanup ----
+ * For cilium_proxy4 / cilium_proxy6: hash maps with key/value sizes 10/16
+ * (proxy4_tbl_key / proxy4_tbl_value) or 22/28 (the v6 pair, bpf/lib/common.h:445-475);
+ * anything else is -EINVAL (gf_ct_gc in turn refuses these maps), a handle that is not a
+ * map -EBADF.  Both run on the host shadow while it is authoritative (no device needed),
+ * else as a sweep of the device replica that compacts the probe clusters it empties, with
+ * no whole-table transfer; afterwards the map's element count is exact again, on the
+ * device and in the host's bound of it, so that later classify calls apply their proxy
+ * updates in parallel whenever count + updates <= max_entries.  Synchronous on `stream`,
+ * ordered against the classify calls that use the map on other streams. */
+/* proxymap.GC / Flush (pkg/maps/proxymap/ipv4.go:136-171, ipv6.go): delete every entry with
+ * value.lifetime < filter_time (strict: lifetime == filter_time stays).  Returns the number
+ * deleted (capped at 0x7fffffff) or -errno.  Flush in the reference is gc(math.MaxUint64),
+ * whose uint32(time / 1e9) is 1266874889, not 0xFFFFFFFF; this call takes any u32. */
+int gf_proxy_gc(int map, uint32_t filter_time, void *stream);
+/* cleanupIPv4Redirects / cleanupIPv6Redirects (ipv4.go:173-195): delete every entry whose
+ * key.dport == dport (raw be16, as stored) and key.nexthdr == 6.  Returns the number deleted. */
+int gf_proxy_cleanup_port(int map, uint16_t dport, void *stream);
+
 /* ---- LRU CT maps (BPF_MAP_TYPE_LRU_HASH, bpf/bpf_lxc.c:53-75) ----
  * The kernel evicts from per-CPU LRU lists (the tail of an inactive list kept
  * about as long as the active one) in a nondeterministic order and never fails
