@@ -141,6 +141,20 @@ GF_STAGE_HOST = 7
 GF_PIPE_F_REV_PROXY = 0x10
 
 
+class gf_respond_cfg(C.Structure):
+    _fields_ = [("policy_array", C.c_int), ("flags", C.c_uint32), ("max_len", C.c_uint32)]
+
+
+class gf_respond_batch(C.Structure):
+    _fields_ = [("frames", gf_frames), ("call", C.c_void_p), ("lxc_id", C.c_void_p), ("flow_hash", C.c_void_p)]
+
+
+GF_CALL_NONE, GF_CALL_ARP, GF_CALL_ICMP6_NS, GF_CALL_ICMP6_ECHO_REPLY, GF_CALL_ICMP6_TIME_EXCEEDED = range(5)
+GF_DROP_UNKNOWN_TARGET = 150
+GF_RESPOND_F_NS_TO_STACK = 1 << 0
+GF_REC_EGRESS, GF_REC_PIPELINE = 1, 2
+
+
 class gf_event_ring(C.Structure):
     _fields_ = [("records", C.c_void_p), ("capacity", C.c_uint32), ("count", C.c_void_p)]
 
@@ -188,6 +202,9 @@ _sig("gf_overlay_load", C.c_int, C.POINTER(gf_overlay_cfg))
 _sig("gf_overlay_classify", C.c_int, C.c_int, C.POINTER(gf_overlay_batch), C.c_uint32, VP, VP, VP)
 _sig("gf_host_load", C.c_int, C.POINTER(gf_host_cfg))
 _sig("gf_host_classify", C.c_int, C.c_int, C.POINTER(gf_host_batch), C.c_uint32, VP, VP, VP)
+_sig("gf_respond_load", C.c_int, C.POINTER(gf_respond_cfg))
+_sig("gf_respond", C.c_int, C.c_int, C.POINTER(gf_respond_batch), VP, VP, VP)
+_sig("gf_respond_calls", C.c_int, C.POINTER(gf_frames), VP, C.c_uint32, VP, VP)
 _sig("gf_ct_gc", C.c_int, C.c_int, C.c_uint32, VP)
 _sig("gf_proxy_gc", C.c_int, C.c_int, C.c_uint32, VP)
 _sig("gf_proxy_cleanup_port", C.c_int, C.c_int, C.c_uint16, VP)
@@ -221,7 +238,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

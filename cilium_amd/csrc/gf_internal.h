@@ -102,7 +102,7 @@ struct HTab {
     void rehash(uint64_t new_nslots);
 };
 
-enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost };
+enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond };
 
 struct Obj {
     ObjKind kind;
@@ -237,6 +237,7 @@ struct PolicyArray : Obj {
     std::vector<uint8_t> h_cfgs;       // last uploaded program table (change detection)
     std::vector<uint16_t> h_slot_of;
     bool dirty = true;
+    uint64_t gen = 0;          // bumped by every gf_policy_array_update (ProgRespond's table follows it)
     int noct = 0;              // programs with GF_LXC_F_NO_CONNTRACK: 0 none, 1 some, 2 every one (gf_policy_array_update)
     std::mutex mu;             // one classify call at a time per array (its device image)
     OrderPt ord;
@@ -262,6 +263,17 @@ struct ProgHost : Obj {            // bpf_netdev.c with FROM_HOST: the program o
     std::shared_ptr<Map> lxc;
     std::shared_ptr<PolicyArray> policy;
     ProgHost() : Obj(ObjKind::ProgHost) {}
+};
+
+struct ProgRespond : Obj {         // the ARP / ICMPv6 responder tail calls (gf_respond.h)
+    gf_respond_cfg cfg{};
+    std::shared_ptr<PolicyArray> policy;   // may be null: the node's programs only
+    DevBuf d_slot_of, d_ents;  // uint16[65536] slot -> entry + 1; {NODE_MAC, LXC_ID} per program
+    uint64_t table_gen = 0;
+    bool have_table = false;
+    std::mutex mu;             // one gf_respond call at a time per handle (its device table)
+    OrderPt ord;
+    ProgRespond() : Obj(ObjKind::ProgRespond) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host

@@ -6099,6 +6099,7 @@ int gf_policy_array_update(int array, uint32_t lxc_id, int prog) {
         a->slots.erase(lxc_id);
     }
     a->dirty = true;
+    a->gen++;
     size_t off = 0;                                     // programs without conntrack: none, some, every one
     for (auto &kv : a->slots)
         if (kv.second->cfg.flags & GF_LXC_F_NO_CONNTRACK) off++;
@@ -8409,3 +8410,6 @@ extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return r;
 }
+
+// ---- the ARP / ICMPv6 responder tail calls: k_respond, gf_respond ----
+#include "gf_respond.h"

@@ -17,7 +17,8 @@ import numpy as np
 from . import bpf
 from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
-                   gf_overlay_batch, gf_host_cfg, gf_host_batch)
+                   gf_overlay_batch, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
+                   GF_CALL_ICMP6_TIME_EXCEEDED, GF_REC_EGRESS, GF_REC_PIPELINE)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
                    ("rev_nat", "<u2"), ("new_daddr4", "<u4")])
@@ -145,6 +146,7 @@ class Datapath:
     def __init__(self, sc, pin_prefix=""):
         self.sc = sc
         self.fd = {}
+        self._resp = {}
         for name, m in sc.maps.items():
             fd = bpf.CreateMap(m.type, m.ksz, m.vsz, m.max_entries, m.flags)
             if m.n():
@@ -316,6 +318,57 @@ class Datapath:
                "gf_lxc_egress_classify")
         return out, snap
 
+    # ---- ARP / ICMPv6 responders (the tail calls after a classify call) ----
+    def responder(self, flags=0, max_len=0):
+        """The gf_respond handle over this datapath's cilium_policy array (loaded on first use,
+        one per (flags, max_len))."""
+        key = (flags, max_len)
+        if key not in self._resp:
+            cfg = gf_respond_cfg(self.policy_array or 0, flags, max_len)
+            self._resp[key] = _check(lib.gf_respond_load(C.byref(cfg)), "gf_respond_load")
+        return self._resp[key]
+
+    def respond(self, frames, len, call, lxc_id=None, flow_hash=None, snap_out=None, flags=0, max_len=0):
+        """gf_respond over frames [n,stride] u8, len [n] i32, call [n] u8 (device tensors); lxc_id
+        [n] i16: the endpoints whose objects make the calls, None = the node's programs.  Returns
+        (records [n,8] u8, snap_out [n,stride] u8); rows of frames without a call keep what snap_out
+        held (a fresh buffer: uninitialised)."""
+        torch = _torch()
+        n = frames.shape[0]
+        out = torch.empty((n, 8), dtype=torch.uint8, device=frames.device)
+        if snap_out is None:
+            snap_out = torch.empty_like(frames)
+        rb = gf_respond_batch(gf_frames(n, frames.shape[1], _ptr(frames), _ptr(len)), _ptr(call), _ptr(lxc_id),
+                              _ptr(flow_hash))
+        _check(lib.gf_respond(self.responder(flags, max_len), C.byref(rb), _ptr(out), _ptr(snap_out), _stream()),
+               "gf_respond")
+        return out, snap_out
+
+    def respond_calls(self, kind, frames, len, records):
+        """gf_respond_calls: the GF_CALL_* column of a classify call's records (kind GF_REC_*)."""
+        torch = _torch()
+        n = frames.shape[0]
+        call = torch.empty(n, dtype=torch.uint8, device=frames.device)
+        fr = gf_frames(n, frames.shape[1], _ptr(frames), _ptr(len))
+        _check(lib.gf_respond_calls(C.byref(fr), _ptr(records), kind, _ptr(call), _stream()), "gf_respond_calls")
+        return call
+
+    def respond_after(self, kind, b, records, snap, flags=0, max_len=0):
+        """The responder tail calls of a classified batch: kind GF_REC_EGRESS (records of
+        egress()) or GF_REC_PIPELINE (pipeline(), overlay(), from_host()), b the DeviceBatch,
+        snap the entry point's snap_out.  ARP, NS and echo frames are taken as received
+        (b.frames); time-exceeded frames as the entry point left them (snap): ipv6_l3 returns
+        before its first write, the programs in front of it (LB, reverse proxy, dmac rewrite)
+        do not.  Egress batches pass the sender's lxc_id, the others the node's NODE_MAC.
+        Returns (call [n] u8, records [n,8] u8, reply frames [n,stride] u8)."""
+        torch = _torch()
+        call = self.respond_calls(kind, b.frames, b.len, records)
+        te = (call == GF_CALL_ICMP6_TIME_EXCEEDED).unsqueeze(1)
+        frames = torch.where(te, snap, b.frames)
+        out, reply = self.respond(frames, b.len, call, b.lxc_id if kind == GF_REC_EGRESS else None, b.flow_hash,
+                                  flags=flags, max_len=max_len)
+        return call, out, reply
+
     # ---- proxy map sweeps (pkg/maps/proxymap: GC / Flush, CleanupOnRedirectClose) ----
     def proxy_gc(self, name, filter_time):
         """gf_proxy_gc on the current stream: deletes lifetime < filter_time, returns the count."""
@@ -338,7 +391,7 @@ class Datapath:
     def close(self):
         """Close the program objects, then the maps (a program holds its maps, so
         their device tables are released once both are closed)."""
-        progs = [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
+        progs = list(self._resp.values()) + [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
         for h in [h for h in progs if h] + list(self.fd.values()):
             try:
                 bpf.ObjClose(h)
@@ -346,6 +399,7 @@ class Datapath:
                 pass
         self.host = self.ovl = self.pipe = self.policy_array = self.lb_prog = self.xdp_prog = None
         self.lxc_progs = []
+        self._resp = {}
         self.fd = {}
 
 

@@ -376,13 +376,14 @@ int gf_policy_ingress_classify_batches(int policy_array, uint32_t nb, const gf_p
  * of the batch (CT, proxy map) precedes every handle_policy effect of its
  * deliveries.  IPv6 frames run tail_handle_ipv6 -> ipv6_l3_from_lxc
  * (:120-416).  Frames for the ARP / ICMPv6 responders (tail_handle_arp,
- * icmp6_handle's NS and echo-to-router) are reported as stage GF_STAGE_NONE. */
+ * icmp6_handle's NS and echo-to-router) are reported as stage GF_STAGE_NONE;
+ * gf_respond_calls + gf_respond (below) run those tail calls. */
 typedef struct gf_lxc_batch {
     gf_frames frames;          /* DEVICE frames (snap_stride >= every header byte touched, <= 256) */
     const uint16_t *lxc_id;    /* DEVICE: the sending endpoint (whose from-container program runs) */
     const uint32_t *flow_hash; /* DEVICE get_hash_recalc(skb) (lb4_select_slave), may be NULL */
 } gf_lxc_batch;
-#define GF_STAGE_NONE     0    /* not classified: ARP / ICMPv6 responders */
+#define GF_STAGE_NONE     0    /* not classified: ARP / ICMPv6 responders (gf_respond) */
 #define GF_STAGE_FROM_LXC 5    /* the from-container verdict is final */
 /* GF_STAGE_POLICY (4): delivered locally, handle_policy of endpoint lxc_id */
 #define GF_EG_F_CREATED   0x0001  /* ct_create4(CT_EGRESS) */
@@ -399,7 +400,7 @@ typedef struct gf_lxc_batch {
 #define GF_EG_F_ARP       0x0800  /* stage NONE: ARP (tail_handle_arp, the responder) */
 #define GF_EG_F_IPV6      0x1000  /* the IPv6 path (ipv6_l3_from_lxc) */
 #define GF_EG_F_ICMP6_TE  0x2000  /* hop limit reached in ipv6_l3: icmp6_send_time_exceeded (action
-                                     REDIRECT; the reply itself is not built) */
+                                     REDIRECT; gf_respond builds the reply, GF_CALL_ICMP6_TIME_EXCEEDED) */
 #define GF_EG_F_RESPONDER 0x4000  /* stage NONE: icmp6_handle's NS / echo-to-router responders */
 typedef struct gf_egress_out {   /* 24 B; bytes 0-9 as gf_pipeline_out */
     uint8_t  stage;       /* GF_STAGE_FROM_LXC / GF_STAGE_POLICY / GF_STAGE_NONE */
@@ -461,7 +462,7 @@ typedef struct gf_pipe_batch {
 #define GF_STAGE_NETDEV 3      /* bpf_netdev verdict is final (to the stack, SHOT, ICMPv6 reply) */
 #define GF_STAGE_POLICY 4      /* tail-called into cilium_policy: handle_policy's verdict */
 #define GF_PIPE_F_ICMP6_TE  0x20  /* hop limit reached: icmp6_send_time_exceeded (bpf/lib/icmp6.h:313-322);
-                                     action REDIRECT, the reply frame itself is not built */
+                                     action REDIRECT; gf_respond builds the reply (GF_CALL_ICMP6_TIME_EXCEEDED) */
 #define GF_PIPE_F_LB        0x40  /* translated by lb*_xlate */
 #define GF_PIPE_F_PORTMAP   0x80  /* dport rewritten by map_lxc_in */
 typedef struct gf_pipeline_out {   /* 24 B */
@@ -609,6 +610,87 @@ typedef struct gf_host_batch {
  * (snap_stride < 14 or > 256), -E2BIG; n == 0 returns 0. */
 int gf_host_classify(int host, const gf_host_batch *batch, uint32_t now_sec,
                      gf_pipeline_out *out, uint8_t *snap_out, void *stream);
+
+/* ---- ARP and ICMPv6 responders: the reply frames, built on the device ----
+ * The four responder tail calls of the reference, run after a classify call over
+ * the frames it reported for them:
+ *   egress records   GF_STAGE_NONE + GF_EG_F_ARP         -> GF_CALL_ARP
+ *                    GF_STAGE_NONE + GF_EG_F_RESPONDER   -> GF_CALL_ICMP6_NS (ICMPv6 type 135) /
+ *                                                           GF_CALL_ICMP6_ECHO_REPLY
+ *                    GF_EG_F_ICMP6_TE                    -> GF_CALL_ICMP6_TIME_EXCEEDED
+ *   pipeline, overlay and from-host records GF_PIPE_F_ICMP6_TE -> GF_CALL_ICMP6_TIME_EXCEEDED
+ * nh_off is ETH_HLEN at every call site.  IPV4_GATEWAY and ROUTER_IP come from
+ * gf_node_config; NODE_MAC from the program in slot lxc_id[i] of the responder's
+ * cilium_policy array (gf_lxc_cfg.node_mac), or from gf_node_cfg.node_mac when the
+ * batch has no lxc_id column.
+ *   ARP (arp_respond): len < 42 TC_ACT_OK; a request (ar_op 1, ar_hrd 1) to the broadcast
+ *     address or NODE_MAC for IPV4_GATEWAY is answered in place (action REDIRECT);
+ *     anything else TC_ACT_OK, untouched.  DROP_ALL endpoints answer too.
+ *   NS (__icmp6_handle_ns): target (bytes 62..78) unreadable DROP_INVALID; not ROUTER_IP
+ *     DROP_UNKNOWN_TARGET (TC_ACT_OK under GF_RESPOND_F_NS_TO_STACK); else a neighbour
+ *     advertisement (type 136, router + solicited, target link-layer option NODE_MAC;
+ *     option bytes 78..86 unreadable: DROP_INVALID after the header was rewritten).
+ *   ECHO_REPLY (__icmp6_send_echo_reply): type 129, identifier and sequence kept.  The
+ *     daddr == ROUTER_IP test belongs to the caller (icmp6_handle) and is not repeated.
+ *   TIME_EXCEEDED (__icmp6_send_time_exceeded, HAVE_SKB_CHANGE_TAIL): embeds the IPv6
+ *     header and 8 (ICMPv6, UDP) or 20 (TCP) upper bytes; other next headers
+ *     DROP_UNKNOWN_L4, unreadable upper bytes DROP_INVALID (both after nexthdr was set to 58);
+ *     new_len = len + 56|68 - ntohs(payload_len) in u32; < 54 or > max_len DROP_WRITE_ERROR
+ *     (skb_change_tail), as is a payload that no longer fits new_len.  Growth is zero-filled.
+ *   The three ICMPv6 calls end in icmp6_send_reply: saddr = ROUTER_IP, daddr = old saddr,
+ *     dmac = old smac, smac = NODE_MAC, the checksum adjusted by csum_diff, action REDIRECT
+ *     (back out skb->ifindex, which has no output column).
+ * Incremental checksum updates keep a wrong request checksum wrong, as the reference does.
+ * A frame that fails midway keeps its partial rewrites in snap_out.  With an event ring
+ * set every SHOT appends one drop record (send_drop_notify_error: labels, dst_id and
+ * ifindex 0; source = LXC_ID of the calling endpoint's program, 0 for the node's; len_orig
+ * the length at the error; the payload the frame as it stood then).  The responders send
+ * no trace records.  Missed tail calls: a call value above 4, or an lxc_id whose slot holds
+ * no program (every slot, for a responder without a policy array): SHOT with
+ * GF_DROP_MISSED_TAIL_CALL, the frame's row in snap_out not written.  Call 0: the record is
+ * {OK, 0, 0, 0, len} and the row in snap_out is not written (the caller's bytes stay). */
+#define GF_CALL_NONE                 0
+#define GF_CALL_ARP                  1  /* tail_handle_arp            bpf/bpf_lxc.c:692-696, lib/arp.h:34-95 */
+#define GF_CALL_ICMP6_NS             2  /* tail_icmp6_handle_ns       lib/icmp6.h:146-199, 331-361 */
+#define GF_CALL_ICMP6_ECHO_REPLY     3  /* tail_icmp6_send_echo_reply lib/icmp6.h:84-127 */
+#define GF_CALL_ICMP6_TIME_EXCEEDED  4  /* tail_icmp6_send_time_exceeded lib/icmp6.h:201-312 (HAVE_SKB_CHANGE_TAIL) */
+#define GF_DROP_UNKNOWN_TARGET 150      /* bpf/lib/common.h:244 */
+
+#define GF_RESPOND_F_NS_TO_STACK (1u << 0) /* ACTION_UNKNOWN_ICMP6_NS = TC_ACT_OK (bpf_netdev.c:25);
+                                              clear: DROP_UNKNOWN_TARGET (icmp6.h:34-36, the bpf_lxc build) */
+typedef struct gf_respond_cfg {
+    int      policy_array;  /* NODE_MAC of the calling endpoint's program; 0 = none */
+    uint32_t flags;         /* GF_RESPOND_F_* (other bits: -EINVAL) */
+    uint32_t max_len;       /* skb_change_tail's upper bound (dev->mtu + hard_header_len); 0 = 1514 */
+} gf_respond_cfg;
+int gf_respond_load(const gf_respond_cfg *cfg);
+
+typedef struct gf_respond_batch {
+    gf_frames       frames;    /* DEVICE; each frame as it stood at the tail call */
+    const uint8_t  *call;      /* DEVICE, GF_CALL_* per frame; required */
+    const uint16_t *lxc_id;    /* DEVICE, the endpoint whose object makes the call; NULL = the node's
+                                  programs (NODE_MAC from gf_node_config) */
+    const uint32_t *flow_hash; /* DEVICE, may be NULL (drop records' hash) */
+} gf_respond_batch;
+typedef struct gf_respond_out {   /* 8 B */
+    uint8_t  action;   /* TC_ACT_REDIRECT = the reply goes back out skb->ifindex; OK; SHOT */
+    uint8_t  reason;   /* -DROP_* when SHOT */
+    uint8_t  call;     /* the call that ran (echo of the column) */
+    uint8_t  pad;
+    uint32_t len;      /* skb->len after the call (changes only for TIME_EXCEEDED) */
+} gf_respond_out;
+/* snap_out (n * snap_stride, required, not frames.snap): the rows of the frames with a call, as
+ * the call left them; bytes of a TIME_EXCEEDED row at or past the new length are 0.
+ * -EBADF (not a responder handle), -EFAULT (a NULL batch, frame pointer, call, out or snap_out),
+ * -EINVAL (snap_stride outside 122..256 = 14 + 40 + 68, the furthest byte a call touches;
+ * snap_out == frames.snap), -E2BIG; n == 0 returns 0.  Every refusal precedes any launch. */
+int gf_respond(int resp, const gf_respond_batch *batch, gf_respond_out *out, uint8_t *snap_out, void *stream);
+
+#define GF_REC_EGRESS   1   /* gf_egress_out  */
+#define GF_REC_PIPELINE 2   /* gf_pipeline_out (pipeline, overlay, from-host) */
+/* call[i] (DEVICE, n bytes) from the records of a classify call over `frames`, by the table above;
+ * everything else GF_CALL_NONE.  -EFAULT, -EINVAL (rec_kind), -E2BIG; n == 0 returns 0. */
+int gf_respond_calls(const gf_frames *frames, const void *records, uint32_t rec_kind, uint8_t *call, void *stream);
 
 /* ---- ingest re-partition for N GPUs (real traffic) ----
  * owner[i] = the rank owning packet i's flow group: the unordered address pair
