@@ -139,6 +139,10 @@ class gf_host_batch(C.Structure):
 
 GF_STAGE_HOST = 7
 GF_PIPE_F_REV_PROXY = 0x10
+GF_NETDEV_F_HANDLE_NS = 1 << 2
+GF_NETDEV_F_ENCAP = 1 << 3
+GF_PIPE_F_RESPONDER = 0x04
+GF_PIPE_F_ENCAP = 0x08
 
 
 class gf_respond_cfg(C.Structure):
@@ -198,6 +202,7 @@ _sig("gf_policy_ingress_classify_batches", C.c_int, C.c_int, C.c_uint32, C.POINT
      C.POINTER(C.c_uint32), C.POINTER(VP), VP)
 _sig("gf_pipeline_load", C.c_int, C.POINTER(gf_pipeline_cfg))
 _sig("gf_pipeline_classify", C.c_int, C.c_int, C.POINTER(gf_pipe_batch), C.c_uint32, VP, VP, VP, VP)
+_sig("gf_pipeline_classify_tunnel", C.c_int, C.c_int, C.POINTER(gf_pipe_batch), C.c_uint32, VP, VP, VP, VP, VP)
 _sig("gf_overlay_load", C.c_int, C.POINTER(gf_overlay_cfg))
 _sig("gf_overlay_classify", C.c_int, C.c_int, C.POINTER(gf_overlay_batch), C.c_uint32, VP, VP, VP)
 _sig("gf_host_load", C.c_int, C.POINTER(gf_host_cfg))
@@ -238,7 +243,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

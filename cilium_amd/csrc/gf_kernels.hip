@@ -2922,6 +2922,39 @@ __device__ int host_reverse_proxy(const HostDev &H, Row &w, uint32_t len, bool v
     return 0;
 }
 
+// The ENCAP_IFINDEX branch of handle_ipv4 (:378-393) / handle_ipv6 (:225-243) once the
+// endpoint lookup missed: the cluster-range test and encap_and_redirect's tunnel-map lookup
+// (lib/encap.h:30-70).  true: tun_ip = bpf_tunnel_key.remote_ipv4; false: not in the range, or
+// DROP_NO_TUNNEL_ENDPOINT, which both callers turn into TC_ACT_OK.  Shared with the pipeline's
+// netdev stage (k_nd_front).
+__device__ __forceinline__ bool host_encap4(const HostDev &H, uint32_t da, uint32_t &tun_ip, uint32_t &ab) {
+    if (H.encap_ifindex && (da & H.cluster_mask) == H.cluster_range) {
+        uint32_t tk[5] = {da & H.ipv4_mask, 0, 0, 0, 1u};
+        const int64_t ft = H.tnset ? aset_slot(H.tnset, H.tnbits, H.tnzero, tk[0]) : ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
+        ab += 20;
+        if (ft >= 0) {                                  // encap_and_redirect (lib/encap.h:30-70)
+            tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
+            ab += 20;
+            return true;
+        }
+    }
+    return false;
+}
+__device__ __forceinline__ bool host_encap6(const HostDev &H, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t &tun_ip,
+                                            uint32_t &ab) {
+    if (H.encap_ifindex && d0 == H.node6[0] && d1 == H.node6[1] && d2 == H.node6[2]) {
+        uint32_t tk[5] = {d0, d1, d2, 0u, 2u};          // daddr/96
+        const int64_t ft = ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
+        ab += 20;
+        if (ft >= 0) {
+            tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
+            ab += 20;
+            return true;
+        }
+    }
+    return false;
+}
+
 __device__ int host_program(const HostDev &H, Row &w, const PktHdr &h, uint32_t et, uint32_t len, uint32_t pid,
                             uint32_t &sec, uint32_t &rev, uint32_t &tun_ip, uint32_t &ifx, uint32_t &lxc,
                             uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
@@ -2948,16 +2981,7 @@ __device__ int host_program(const HostDev &H, Row &w, const PktHdr &h, uint32_t 
             ab += 3;
             return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
         }
-        if (H.encap_ifindex && (da & H.cluster_mask) == H.cluster_range) {   // ENCAP_IFINDEX (:378-393)
-            uint32_t tk[5] = {da & H.ipv4_mask, 0, 0, 0, 1u};
-            const int64_t ft = H.tnset ? aset_slot(H.tnset, H.tnbits, H.tnzero, tk[0]) : ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
-            ab += 20;
-            if (ft >= 0) {                              // encap_and_redirect (lib/encap.h:30-70)
-                tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
-                ab += 20;
-                return HO_ENCAP;
-            }
-        }
+        if (host_encap4(H, da, tun_ip, ab)) return HO_ENCAP;   // ENCAP_IFINDEX (:378-393)
         return TC_OK;                                   // :395
     }
     if (et == 0x86DD) {
@@ -2985,16 +3009,7 @@ __device__ int host_program(const HostDev &H, Row &w, const PktHdr &h, uint32_t 
             ab += 1;
             return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
         }
-        if (H.encap_ifindex && d0 == H.node6[0] && d1 == H.node6[1] && d2 == H.node6[2]) {   // :225-243
-            uint32_t tk[5] = {d0, d1, d2, 0u, 2u};      // daddr/96
-            const int64_t ft = ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
-            ab += 20;
-            if (ft >= 0) {
-                tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
-                ab += 20;
-                return HO_ENCAP;
-            }
-        }
+        if (host_encap6(H, d0, d1, d2, tun_ip, ab)) return HO_ENCAP;   // :225-243
         return TC_OK;                                   // :245
     }
     return TC_OK;                                       // unknown traffic to the stack (:462-464)
@@ -3094,6 +3109,228 @@ __global__ __launch_bounds__(NT) void k_host_front(gf_frames fr, const uint32_t 
         uint8_t *dst = snap_out + (size_t)b0 * S;
         size_t k0 = 0;
         if (H.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
+    }
+    if (stats) st.flush(stats);
+}
+
+// ================================================================ netdev stage with HANDLE_NS / ENCAP_IFINDEX
+// from_netdev as bpf/init.sh builds it for the native device (:179 -DHANDLE_NS; ENCAP_IFINDEX
+// from node_config.h in tunnel mode, :303-304): pipe_netdev with icmp6_handle
+// (bpf_netdev.c:180-186, lib/icmp6.h:380-401) and the encap branches (:225-243, :378-392).
+// A pipeline that sets neither GF_NETDEV_F_HANDLE_NS nor GF_NETDEV_F_ENCAP never gets here.
+struct NdxDev {
+    HostDev enc;                   // the encap state host_encap4 / 6 read: tunnel, tnset, tnbits, tnzero,
+                                   // encap_ifindex, cluster_range / _mask, ipv4_mask, node6 (the rest unset)
+    uint32_t router6[4];           // ROUTER_IP (gf_netdev_cfg.router_ip6): icmp6_handle's echo test
+    uint32_t *tunnel_ip;           // bpf_tunnel_key.remote_ipv4 per frame (0: no encap), or null
+};
+enum { ND_RESPOND = 1004 };
+
+__device__ int pipe_netdev_x(const NetdevDev &N, const NdxDev &X, Row &w, const PktHdr &h, uint32_t et, uint32_t len,
+                             uint32_t &sec, uint32_t &call, uint32_t &tun_ip, uint32_t &ifx, uint32_t &lxc,
+                             uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
+    const bool encap = N.flags & GF_NETDEV_F_ENCAP;
+    if (et == 0x0800) {
+        if (len < 34) return D_INVALID;                 // revalidate_data
+        sec = (N.flags & GF_NETDEV_F_FIXED_SECCTX) ? N.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
+        const uint32_t da = w.r32(30);                  // post-LB daddr
+        uint32_t kw[5] = {da, 0, 0, 0, 1u};             // lookup_ip4_endpoint
+        const int64_t f = N.lxset ? aset_slot(N.lxset, N.lxbits, N.lxzero, kw[0]) : ht_find<20>(N.lxc, kw, key_hash<20>(kw));
+        ab += 20;
+        if (f < 0) {
+            if (encap && host_encap4(X.enc, da, tun_ip, ab)) return HO_ENCAP;   // :378-392
+            return TC_OK;
+        }
+        const uint8_t *ep = ht_val(N.lxc, f);
+        ab += 8;
+        if (gload<uint32_t>(ep + 8) & 1u) return TC_OK; // ENDPOINT_F_HOST
+        const uint32_t ttl = w.b(22);                   // ipv4_dec_ttl, bpf/lib/ipv4.h:30-43
+        if (ttl <= 1) return D_INVALID;
+        l3_csum(w, len, 24, ttl, ttl - 1, 2);
+        w.w8(22, ttl - 1);
+        ab += 3;
+        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+    }
+    if (et == 0x86DD) {
+        if (len < 54) return D_INVALID;
+        // HANDLE_NS (:180-186): nexthdr as ipv6_hdrlen left it (h.proto: a rejected chain keeps
+        // ip6->nexthdr, never 58).  icmp6_load_type (icmp6.h:38-41) is load_byte at the fixed
+        // ETH_HLEN + 40, also behind extension headers; a load past the frame ends the program
+        // with 0 = TC_ACT_OK.
+        if ((N.flags & GF_NETDEV_F_HANDLE_NS) && h.proto == 58) {
+            if (len < 55) return TC_OK;
+            const uint32_t type = w.b(54);
+            ab += 1;
+            if (type == 135) { call = GF_CALL_ICMP6_NS; return ND_RESPOND; }   // icmp6_handle_ns (:389-390)
+            if (type == 128 && w.r32(38) == X.router6[0] && w.r32(42) == X.router6[1] && w.r32(46) == X.router6[2] &&
+                w.r32(50) == X.router6[3]) {            // :391-393
+                call = GF_CALL_ICMP6_ECHO_REPLY;
+                return ND_RESPOND;
+            }
+        }
+        sec = 2u;                                       // derive_sec_ctx (bpf_netdev.c:50-64)
+        if (N.flags & GF_NETDEV_F_FIXED_SECCTX) sec = N.fixed_secctx;
+        else if (w.r32(22) == N.router6[0] && w.r32(26) == N.router6[1])
+            sec = __builtin_bswap32(w.r32(14) & __builtin_bswap32(0x000FFFFFu));
+        const uint32_t d0 = w.r32(38), d1 = w.r32(42), d2 = w.r32(46);
+        uint32_t kw[5] = {d0, d1, d2, w.r32(50), 2u};
+        const int64_t f = ht_find<20>(N.lxc, kw, key_hash<20>(kw));
+        ab += 20 + 8;
+        if (f < 0) {
+            if (encap && host_encap6(X.enc, d0, d1, d2, tun_ip, ab)) return HO_ENCAP;   // :225-243
+            return TC_OK;
+        }
+        const uint8_t *ep = ht_val(N.lxc, f);
+        ab += 8;
+        if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;
+        const uint32_t hl = w.b(21);                    // ipv6_dec_hoplimit, bpf/lib/ipv6.h:178-193
+        if (hl <= 1) return ND_ICMP6_TE;
+        w.w8(21, hl - 1);
+        ab += 1;
+        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+    }
+    return TC_OK;                                       // unknown traffic to the stack
+}
+
+// The sibling of k_pipe_front for a pipeline whose netdev stage has GF_NETDEV_F_HANDLE_NS or
+// GF_NETDEV_F_ENCAP: the same three programs on the lane's LDS row and the same gf_rec / key /
+// record triple, with pipe_netdev_x in place of pipe_netdev.  Like k_ovl_front and k_host_front
+// it is not held to k_pipe_front's 64 VGPRs (<= 32 KiB of LDS rows: five blocks per CU).
+template <int NT>
+__global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
+                                                 PipeDev P, NdxDev X, const uint16_t *slot_of, gf_rec *rec,
+                                                 uint32_t *keys, uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
+                                                 uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats) {
+    extern __shared__ uint4 lds_rows[];
+    uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
+    __shared__ uint32_t sl[272];
+    Stats st{sl};
+    if (stats) st.init();
+    const uint32_t S = fr.snap_stride;
+    const uint32_t b0 = blockIdx.x * NT;
+    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
+    const size_t bytes = (size_t)nb * S;
+    {
+        const uint8_t *src = fr.snap + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (P.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
+    }
+    __syncthreads();
+    const uint32_t i = b0 + threadIdx.x;
+    bool scnt = false;                                  // the lane's counter-block entry
+    uint32_t sreason = 0, saction = 0, slen = 0, sab = 0;
+    if (i < fr.n) {
+        const uint32_t len = fr.len[i];
+        const uint32_t cap = S < len ? S : len;
+        Row w{rows + (size_t)threadIdx.x * S, cap};
+        PktHdr h;
+        parse_row(w.p, cap, len, h);
+        const uint32_t et = h.et;
+        const PktHdrA ha{h, flow_hash ? flow_hash[i] : 0u};
+        gf_pipeline_out o{};
+        uint32_t n6[4] = {0, 0, 0, 0};
+        uint32_t sec = 0, call = 0, tun_ip = 0, ifx = 0, lxc = 0, mapped = 0, ndport = 0;
+        uint32_t ab = 24 + 34;                          // output record, header bytes parsed
+        bool tail = false, enc = false;
+        do {
+            if (P.has_xdp && xdp_verdict(P.x, ha, len, et, ab) == XDP_DROP_) {
+                o.stage = GF_STAGE_XDP; o.action = XDP_DROP_;
+                break;
+            }
+            if (P.has_lb) {
+                gf_lb_out lo{};
+                uint32_t kd = 0;
+                int ret = TC_OK;
+                bool v6 = false;
+                ab += 12;
+                if (et == 0x86DD) {
+                    if (!(P.L.flags & GF_LB_F_NO_IPV6)) { v6 = true; ab += 28; ret = lb_v6(P.L, ha, len, lo, n6, ab, kd); }
+                } else if (et == 0x0800) {
+                    if (!(P.L.flags & GF_LB_F_NO_IPV4)) ret = lb_v4(P.L, ha, len, lo, ab, kd);
+                }
+                if (ret < 0 || ret == TC_SHOT) {
+                    o.stage = GF_STAGE_LB; o.action = TC_SHOT; o.reason = (uint8_t)(-ret);
+                    n6[0] = n6[1] = n6[2] = n6[3] = 0;
+                    break;
+                }
+                if (ret == TC_REDIRECT) {
+                    pipe_lb_rewrite(w, len, h, v6, lo, n6, kd, ab);
+                    o.slave = lo.slave; o.rev_nat = lo.rev_nat; o.dport = lo.new_dport;
+                    o.daddr4 = v6 ? 0u : lo.new_daddr4;
+                    o.flags |= GF_PIPE_F_LB;
+                    if (P.L.flags & GF_LB_F_REDIRECT) {
+                        o.stage = GF_STAGE_LB; o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)P.lb_redirect_ifindex;
+                        break;
+                    }
+                } else {
+                    n6[0] = n6[1] = n6[2] = n6[3] = 0;
+                }
+            }
+            if (P.tcap_in) {                            // from_netdev's send_trace_notify (bpf_netdev.c:436)
+                uint8_t *d = P.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
+                const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
+                if (P.vec_copy) {
+                    for (uint32_t k = 0; k < cb; k += 16)
+                        *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
+                } else {
+                    for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
+                }
+            }
+            const int r = pipe_netdev_x(P.nd, X, w, h, et, len, sec, call, tun_ip, ifx, lxc, mapped, ndport, ab);
+            if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
+            o.stage = GF_STAGE_NETDEV;
+            if (r == ND_TAILCALL) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; tail = true; }
+            else if (r == ND_RESPOND) { o.flags |= GF_PIPE_F_RESPONDER; o.pad0 = (uint8_t)call; }   // action OK, reason 0 (as eg_front6)
+            else if (r == HO_ENCAP) {
+                o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)X.enc.encap_ifindex; o.flags |= GF_PIPE_F_ENCAP;
+                enc = true;
+            }
+            else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
+            else if (r < 0 || r == TC_SHOT) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }
+            else o.action = (uint8_t)r;
+        } while (0);
+        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
+        gf_rec rr;
+        uint32_t key;
+        const uint32_t tci = tc_index ? tc_index[i] : 0u;
+        if (tail) {
+            PktHdr h2;
+            parse_row(w.p, cap, len, h2);
+            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx, slot_of[lxc & 0xffffu],
+                           tci, false, true, h2.s6, h2.d6, rr);
+            rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);   // the front's flags for IngCtx::pout_wo, as k_pipe_front
+            if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
+                reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
+                reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
+            }
+        } else {
+            // an encap redirect keeps its secctx in the (skipped) record: TRACE_TO_OVERLAY's label
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, enc ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr);
+        }
+        rec[i] = rr;
+        keys[i] = key;
+        out[i] = o;
+        if (nd6) reinterpret_cast<uint4 *>(nd6)[i] = make_uint4(n6[0], n6[1], n6[2], n6[3]);
+        if (X.tunnel_ip) X.tunnel_ip[i] = tun_ip;
+        sab = ab;                                       // a tail-called packet: handle_policy counts it
+        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
+    }
+    if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
+    if (snap_out) {
+        __syncthreads();
+        uint8_t *dst = snap_out + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (P.vec_copy) {
             const size_t nv = bytes / 16;
             for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
             k0 = nv * 16;
@@ -3969,12 +4206,14 @@ __device__ uint32_t ev_list(const EvSrc &E, uint32_t i, int k, EvOne &out) {
         if (E.kind == 1 && E.nd_trace && (stage == (E.nd_trace >> 8) || stage == GF_STAGE_POLICY)) {
             uint32_t obs = E.nd_trace & 0xffu, src = 0;
             const uint8_t *cin = E.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
+            // the fronts capture min(snap_stride, 128) bytes of the row: the rest of the slot is not the frame's
+            const uint32_t cst = E.snap_stride < GF_TRACE_PAYLOAD_LEN ? E.snap_stride : GF_TRACE_PAYLOAD_LEN;
             if (obs == TR_FROM_HOST) {                      // bpf_netdev.c:423-433: report_identity
                 uint32_t skip;
                 const uint32_t pid = host_mark_identity(E.hmark ? E.hmark[i] : 0u, skip);
                 src = 1u;                                   // HOST_ID
                 if (pid) { obs = TR_FROM_PROXY; src = pid; }
-                put(ev_trace(obs, 0, hash, len, src, 0, 0, E.nd_ifindex, 0, cin, GF_TRACE_PAYLOAD_LEN));
+                put(ev_trace(obs, 0, hash, len, src, 0, 0, E.nd_ifindex, 0, cin, cst));
                 if (stage == GF_STAGE_HOST && act == TC_REDIRECT && !(ofl & GF_PIPE_F_ICMP6_TE)) {
                     // encap_and_redirect's TRACE_TO_OVERLAY (encap.h:67) with the packet's secctx,
                     // which the front left in the record it packed
@@ -3982,7 +4221,10 @@ __device__ uint32_t ev_list(const EvSrc &E, uint32_t i, int k, EvOne &out) {
                                  E.snap_stride));
                 }
             } else {
-                put(ev_trace(obs, 0, hash, len, 0, 0, 0, E.nd_ifindex, 0, cin, GF_TRACE_PAYLOAD_LEN));
+                put(ev_trace(obs, 0, hash, len, 0, 0, 0, E.nd_ifindex, 0, cin, cst));
+                if (stage == GF_STAGE_NETDEV && (ofl & GF_PIPE_F_ENCAP))   // GF_NETDEV_F_ENCAP's redirect (encap.h:67), as above
+                    put(ev_trace(TR_TO_OVERLAY, 0, hash, len, E.prec[i].src_identity, 0, 0, E.encap_ifindex, 0, fin,
+                                 E.snap_stride));
             }
         }
         if (E.kind == 2) {
@@ -7152,6 +7394,8 @@ int gf_pipeline_load(const gf_pipeline_cfg *cfg) {
     if (!m) return -EBADF;
     if (m->ksz != 20 || m->vsz != 112 || m->is_lpm()) return -EINVAL;
     p->lxc = m;
+    // ENCAP_IFINDEX for the netdev stage is the node's: it must be defined, with a tunnel map to look up
+    if ((cfg->netdev.flags & GF_NETDEV_F_ENCAP) && (!node_cfg().encap_ifindex || !node_map(2))) return -EINVAL;
     auto a = get_obj(cfg->policy_array);
     if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
     p->policy = std::static_pointer_cast<PolicyArray>(a);
@@ -7160,6 +7404,11 @@ int gf_pipeline_load(const gf_pipeline_cfg *cfg) {
 
 int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_pipeline_out *out,
                          uint8_t *nd6, uint8_t *snap_out, void *stream) {
+    return gf_pipeline_classify_tunnel(pipe, b, now_sec, out, nd6, snap_out, nullptr, stream);
+}
+
+int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_pipeline_out *out,
+                                uint8_t *nd6, uint8_t *snap_out, uint32_t *tunnel_ip, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
     auto o = get_obj(pipe);
     if (!o || o->kind != ObjKind::ProgPipe) return -EBADF;
@@ -7213,6 +7462,28 @@ int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_
     P.nd.flags = p->cfg.netdev.flags;
     P.nd.fixed_secctx = p->cfg.netdev.fixed_secctx;
     memcpy(P.nd.router6, p->cfg.netdev.router_ip6, 8);
+    // GF_NETDEV_F_HANDLE_NS / _ENCAP: the sibling front (k_nd_front); neither set: k_pipe_front as ever
+    const bool ndx = p->cfg.netdev.flags & (GF_NETDEV_F_HANDLE_NS | GF_NETDEV_F_ENCAP);
+    NdxDev X{};
+    if (ndx) {
+        memcpy(X.router6, p->cfg.netdev.router_ip6, 16);
+        X.tunnel_ip = tunnel_ip;
+        if (p->cfg.netdev.flags & GF_NETDEV_F_ENCAP) {
+            const gf_node_cfg &node = node_cfg();
+            auto tun = node_map(2);
+            if (!tun || !node.encap_ifindex) return -EINVAL;   // the node was reconfigured since gf_pipeline_load
+            if ((r = push_map(tun, s))) return r;
+            X.enc.tunnel = tun->hdesc();
+            if (getenv("GF_XDP_NOSETS") || tun->addr_set(20, 8192, s, &X.enc.tnset, &X.enc.tnbits, &X.enc.tnzero))
+                X.enc.tnset = nullptr;
+            X.enc.encap_ifindex = node.encap_ifindex;
+            X.enc.cluster_range = node.ipv4_cluster_range; X.enc.cluster_mask = node.ipv4_cluster_mask;
+            X.enc.ipv4_mask = node.ipv4_mask;
+            memcpy(X.enc.node6, node.router_ip6, 12);
+        }
+    } else if (tunnel_ip) {
+        if (hip_ok(hipMemsetAsync(tunnel_ip, 0, (size_t)n * 4, s), "tunnel_ip")) return -EIO;
+    }
     // LDS staging of the block's frames (one row per lane)
     // (256 lanes per block up to 128-B snaps, 128 lanes up to 256 B: <= 32 KiB)
     if (fr.snap_stride > 256) return -EINVAL;          // not a header snap
@@ -7235,6 +7506,16 @@ int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_
     c2.n = n;
     c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
     auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
+        if (ndx) {
+            ProfScope ps("k_nd_front", s);
+            if (nt == 256)
+                hipLaunchKernelGGL(k_nd_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tc_index, b->flow_hash, P, X,
+                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
+            else
+                hipLaunchKernelGGL(k_nd_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tc_index, b->flow_hash, P, X,
+                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
+            return hip_ok(hipGetLastError(), "k_nd_front");
+        }
         ProfScope ps("k_pipe_front", s);
         if (nt == 256)
             hipLaunchKernelGGL(k_pipe_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tc_index, b->flow_hash, P,

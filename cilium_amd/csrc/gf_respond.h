@@ -288,6 +288,8 @@ __global__ __launch_bounds__(BLOCK) void k_respond_calls(gf_frames fr, const uin
         } else if (ef & GF_EG_F_ICMP6_TE) c = GF_CALL_ICMP6_TIME_EXCEEDED;
     } else if (r[4] & GF_PIPE_F_ICMP6_TE) {                                 // gf_pipeline_out.flags
         c = GF_CALL_ICMP6_TIME_EXCEEDED;
+    } else if (r[4] & GF_PIPE_F_RESPONDER) {                                // the netdev front's icmp6_handle
+        c = r[5];                                                           // gf_pipeline_out.pad0
     }
     call[i] = (uint8_t)c;
 }

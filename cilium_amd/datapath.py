@@ -277,6 +277,23 @@ class Datapath:
                "gf_pipeline_classify")
         return out, nd6, snap
 
+    def pipeline_tunnel(self, b, now, out=None, snap_out=True, tunnel_ip=True):
+        """gf_pipeline_classify_tunnel: pipeline() with the tunnel endpoint column of a netdev stage
+        loaded with GF_NETDEV_F_ENCAP.  Returns (records, new_daddr6, rewritten snaps or None,
+        tunnel_ip [n] i32 — bpf_tunnel_key.remote_ipv4, 0 where the frame did not encap — or None
+        when tunnel_ip=False, which passes NULL)."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty((b.n, 24), dtype=torch.uint8, device=b.device)
+        nd6 = torch.empty((b.n, 16), dtype=torch.uint8, device=b.device)
+        snap = torch.empty_like(b.frames) if snap_out else None
+        tun = torch.empty(b.n, dtype=torch.int32, device=b.device) if tunnel_ip else None
+        stride = b.frames.shape[1] if b.n else 64
+        pb = gf_pipe_batch(gf_frames(b.n, stride, _ptr(b.frames), _ptr(b.len)), _ptr(b.tc_index), _ptr(b.flow_hash))
+        _check(lib.gf_pipeline_classify_tunnel(self.pipe, C.byref(pb), now, _ptr(out), _ptr(nd6), _ptr(snap), _ptr(tun),
+                                               _stream()), "gf_pipeline_classify_tunnel")
+        return out, nd6, snap, tun
+
     def overlay(self, b, now, out=None, snap_out=True):
         """from-overlay over the batch's inner frames and tunnel ids (+ handle_policy of
         the local deliveries): returns (records [n,24] u8, rewritten snaps or None)."""
@@ -357,7 +374,10 @@ class Datapath:
         """The responder tail calls of a classified batch: kind GF_REC_EGRESS (records of
         egress()) or GF_REC_PIPELINE (pipeline(), overlay(), from_host()), b the DeviceBatch,
         snap the entry point's snap_out.  ARP, NS and echo frames are taken as received
-        (b.frames); time-exceeded frames as the entry point left them (snap): ipv6_l3 returns
+        (b.frames; the pipeline's GF_PIPE_F_RESPONDER records of a netdev stage with
+        GF_NETDEV_F_HANDLE_NS included: their call comes from the record, and bpf_lb leaves an
+        ICMPv6 frame that matches no service as it came); time-exceeded frames as the entry point
+        left them (snap): ipv6_l3 returns
         before its first write, the programs in front of it (LB, reverse proxy, dmac rewrite)
         do not.  Egress batches pass the sender's lxc_id, the others the node's NODE_MAC.
         Returns (call [n] u8, records [n,8] u8, reply frames [n,stride] u8)."""

@@ -1263,6 +1263,57 @@ def ct6_prefill(meta, reply_keys, reply_vals, now, seed=0xC1D40055):
 LXC_POLICY_EGRESS = 32
 LXC_TRACE_NOTIFY = 64          # TRACE_NOTIFY (pkg/endpoint/endpoint.go:131-134)
 NETDEV_TRACE_NOTIFY = 2
+NETDEV_HANDLE_NS = 4           # GF_NETDEV_F_HANDLE_NS
+NETDEV_ENCAP = 8               # GF_NETDEV_F_ENCAP
+
+
+def netdev_fuzz(seed=3, n_packets=20000, n_batches=3, responders=0.05, remote=0.10, encap_ifindex=7,
+                flags=NETDEV_HANDLE_NS | NETDEV_ENCAP, **kw):
+    """pipeline_fuzz's frames for a native device built as bpf/init.sh builds it (-DHANDLE_NS, and
+    ENCAP_IFINDEX in tunnel mode): host_fuzz's remote-pod destinations and tunnel map (`remote` of
+    the IP frames readdressed into the cluster range outside cilium_lxc, half of the IPv4 /24s and
+    the router's /96 with a tunnel endpoint; empty proxy maps, no mark column), and `responders` of
+    the IPv6 frames rewritten into ICMPv6: neighbour solicitations (target ROUTER_IP or another
+    address), echo requests to ROUTER_IP and to the frame's own destination, other types, some of
+    them cut to 54 bytes (the type byte not loadable), and some behind a hop-by-hop header, where
+    the fixed type offset reads the extension header's next-header byte.  `responders` counts against
+    the whole batch: frames that are not IPv6 get a fresh IPv6 header.  No XDP program; the netdev
+    stage gets `flags` on top of pipeline_fuzz's."""
+    sc = host_fuzz(seed, n_packets, n_batches, reverse=0.0, remote=remote, encap_ifindex=encap_ifindex, **kw)
+    sc.name = f"netdev{seed}"
+    sc.host = None
+    sc.xdp = None          # the prefilter passes local destinations alone: behind it no frame reaches the encap branch
+    lxc = sc.maps["cilium_lxc"]
+    rng = np.random.default_rng(seed ^ 0x4E53)
+    router = np.frombuffer(sc.netdev["router_ip6"], np.uint8)
+    for k, pk in enumerate(sc.batches):
+        f, m = pk.frames, pk.n
+        rows = np.nonzero(rng.random(m) < responders)[0]
+        lens = pk.lens.copy()
+        kind = rng.integers(0, 8, len(rows))
+        ep6 = lxc.keys[(lxc.keys[:, 16] == 2) & (lxc.vals[:, 8] & 1 == 0)][:, :16]
+        for i, kd in zip(rows, kind):
+            if not (f[i, 12] == 0x86 and f[i, 13] == 0xDD and lens[i] >= 54):   # a fresh IPv6 header
+                f[i, 12:22] = (0x86, 0xDD, 0x60, 0, 0, 0, 0, 32, 58, 64)
+                f[i, 22:38] = rng.integers(1, 255, 16)
+                f[i, 38:54] = ep6[rng.integers(0, len(ep6))] if kd % 2 else rng.integers(1, 255, 16)
+            f[i, 20], f[i, 55:86] = 58, 0
+            f[i, 54] = (135, 135, 128, 128, 129, 135, 128, 135)[kd]
+            f[i, 56:58] = rng.integers(0, 256, 2)                       # a checksum
+            f[i, 62:78] = router if kd in (0, 5, 7) else rng.integers(1, 255, 16)   # the NS target
+            f[i, 78:86] = (1, 1, 2, 3, 4, 5, 6, 7)                      # source link-layer option
+            lens[i] = max(int(lens[i]), 86)
+            if kd in (2, 6):
+                f[i, 38:54] = router                                    # echo request to the router
+            if kd == 5:
+                lens[i] = 54                                            # ICMPv6 too short for its type byte
+            if kd in (6, 7):                                            # behind a hop-by-hop header (8 bytes)
+                f[i, 62:94] = f[i, 54:86]
+                f[i, 20], f[i, 54:62] = 0, (58, 0, 1, 4, 0, 0, 0, 0)
+                lens[i] = max(int(lens[i]), 94)
+        sc.batches[k] = Packets(f, lens, pk.src_identity, pk.ifindex, pk.lxc_id, pk.tc_index, pk.flow_hash)
+    sc.netdev = dict(sc.netdev, flags=sc.netdev.get("flags", 0) | flags, ingress_ifindex=4)
+    return sc
 
 
 def egress_fuzz(seed=5, n_packets=20000, n_batches=3, proxy_max=524288, hazard=True, icmp=True):

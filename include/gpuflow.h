@@ -435,6 +435,33 @@ int gf_lxc_egress_classify(int policy_array, const gf_lxc_batch *batch, uint32_t
  * kernel chains the programs), see DESIGN.md. */
 #define GF_NETDEV_F_FIXED_SECCTX (1u << 0)  /* FIXED_SRC_SECCTX defined */
 #define GF_NETDEV_F_TRACE_NOTIFY (1u << 1)  /* TRACE_NOTIFY: TRACE_FROM_STACK at from_netdev (bpf_netdev.c:436) */
+/* The two build options bpf/init.sh gives the native device's object (:179 -DHANDLE_NS always;
+ * node_config.h's ENCAP_IFINDEX in tunnel mode, :303-304).  Both are opt-in for the pipeline's
+ * netdev stage and ignored by gf_host_load; a pipeline loaded without them is from_netdev compiled
+ * without either, whatever gf_node_cfg.encap_ifindex holds.
+ *   HANDLE_NS (bpf_netdev.c:180-186, lib/icmp6.h:38-45, 380-401): in handle_ipv6, after ipv6_hdrlen
+ *     and before derive_sec_ctx, when the next header ipv6_hdrlen arrived at is ICMPv6 (58; a chain
+ *     it rejects leaves ip6->nexthdr, which is never 58): icmp6_handle(skb, ETH_HLEN, ip6).
+ *     icmp6_load_type is load_byte (LD_ABS) at the fixed offset 14 + 40 = 54, also behind extension
+ *     headers, where byte 54 is the first extension header's own next-header field; a load past the
+ *     frame (len 54) ends the program with return value 0 = TC_ACT_OK, the frame untouched and no
+ *     notification.  Type 135: the CILIUM_CALL_HANDLE_ICMP6_NS tail call, whatever the target.
+ *     Type 128 with ip6->daddr (as bpf_lb left it) == gf_netdev_cfg.router_ip6: the
+ *     CILIUM_CALL_SEND_ICMP6_ECHO_REPLY tail call.  Everything else goes on to derive_sec_ctx.
+ *     A frame that takes a tail call ends in the front: stage GF_STAGE_NETDEV, action TC_ACT_OK and
+ *     reason 0 (as the egress front reports its responders), GF_PIPE_F_RESPONDER, the GF_CALL_* number
+ *     in pad0; the frame as bpf_lb left it.  gf_respond_calls + gf_respond run the call (NODE_MAC
+ *     from gf_node_config: no lxc_id column).
+ *   ENCAP (bpf_netdev.c:225-243, 378-392, lib/encap.h:30-70): after the cilium_lxc lookup missed,
+ *     the cluster-range test and encap_and_redirect of gf_host_classify (below), with secctx =
+ *     derive_sec_ctx / derive_ipv4_sec_ctx / FIXED_SRC_SECCTX; a tunnel-map miss falls through to
+ *     TC_ACT_OK.  Record: stage GF_STAGE_NETDEV, action REDIRECT, ifindex_lo = ENCAP_IFINDEX,
+ *     GF_PIPE_F_ENCAP; the tunnel endpoint goes to gf_pipeline_classify_tunnel's tunnel_ip column
+ *     (daddr4 keeps lb4_xlate's address).  With GF_NETDEV_F_TRACE_NOTIFY the redirect appends
+ *     TRACE_TO_OVERLAY (src_label = secctx, ifindex = ENCAP_IFINDEX) after TRACE_FROM_STACK.
+ *     gf_pipeline_load: -EINVAL unless gf_node_cfg.encap_ifindex != 0 and a tunnel map is set. */
+#define GF_NETDEV_F_HANDLE_NS    (1u << 2)  /* HANDLE_NS defined */
+#define GF_NETDEV_F_ENCAP        (1u << 3)  /* ENCAP_IFINDEX defined (= gf_node_cfg.encap_ifindex) */
 typedef struct gf_netdev_cfg {
     int lxc_map;               /* cilium_lxc (endpoint_key 20 B -> endpoint_info 112 B) */
     uint32_t flags;            /* GF_NETDEV_F_* */
@@ -461,6 +488,8 @@ typedef struct gf_pipe_batch {
 #define GF_STAGE_LB     2      /* bpf_lb verdict is final (SHOT, or REDIRECT with LB_REDIRECT) */
 #define GF_STAGE_NETDEV 3      /* bpf_netdev verdict is final (to the stack, SHOT, ICMPv6 reply) */
 #define GF_STAGE_POLICY 4      /* tail-called into cilium_policy: handle_policy's verdict */
+#define GF_PIPE_F_RESPONDER 0x04  /* stage NETDEV, GF_NETDEV_F_HANDLE_NS: icmp6_handle took a responder tail call (pad0) */
+#define GF_PIPE_F_ENCAP     0x08  /* stage NETDEV, GF_NETDEV_F_ENCAP: encap_and_redirect (tunnel_ip column) */
 #define GF_PIPE_F_ICMP6_TE  0x20  /* hop limit reached: icmp6_send_time_exceeded (bpf/lib/icmp6.h:313-322);
                                      action REDIRECT; gf_respond builds the reply (GF_CALL_ICMP6_TIME_EXCEEDED) */
 #define GF_PIPE_F_LB        0x40  /* translated by lb*_xlate */
@@ -471,7 +500,7 @@ typedef struct gf_pipeline_out {   /* 24 B */
     uint8_t  reason;      /* drop reason (cb[2]) when SHOT */
     uint8_t  ct_ret;      /* stage POLICY: CT_NEW/ESTABLISHED/REPLY/RELATED */
     uint8_t  flags;       /* gf_ingress_out.flags | GF_PIPE_F_* */
-    uint8_t  pad0;
+    uint8_t  pad0;        /* GF_PIPE_F_RESPONDER: the GF_CALL_* tail call taken; else 0 */
     uint16_t proxy_port;  /* stage POLICY: raw be16 */
     uint16_t ifindex_lo;  /* redirect target (LB_REDIRECT ifindex, or handle_policy's) */
     uint16_t slave;       /* LB: selected slave */
@@ -486,6 +515,12 @@ typedef struct gf_pipeline_out {   /* 24 B */
  * (MACs, TTL/hop limit, daddr, dport, IPv4 + L4 checksums). */
 int gf_pipeline_classify(int pipe, const gf_pipe_batch *batch, uint32_t now_sec, gf_pipeline_out *out,
                          uint8_t *new_daddr6, uint8_t *snap_out, void *stream);
+/* gf_pipeline_classify with one more optional column: tunnel_ip (DEVICE, n u32, may be NULL) =
+ * bpf_tunnel_key.remote_ipv4 of the frames that took GF_NETDEV_F_ENCAP's redirect, host byte order
+ * as gf_egress_out.tunnel_ip, 0 for every other frame.  A frame load-balanced to a backend on
+ * another node has both daddr4 and tunnel_ip.  gf_pipeline_classify forwards here with NULL. */
+int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *batch, uint32_t now_sec, gf_pipeline_out *out,
+                                uint8_t *new_daddr6, uint8_t *snap_out, uint32_t *tunnel_ip, void *stream);
 
 /* ---- from-overlay: the program on the tunnel device (bpf/bpf_overlay.c:38-200) ----
  * In tunnel mode every cross-node pod-to-pod packet reaches its endpoint
@@ -619,6 +654,8 @@ int gf_host_classify(int host, const gf_host_batch *batch, uint32_t now_sec,
  *                                                           GF_CALL_ICMP6_ECHO_REPLY
  *                    GF_EG_F_ICMP6_TE                    -> GF_CALL_ICMP6_TIME_EXCEEDED
  *   pipeline, overlay and from-host records GF_PIPE_F_ICMP6_TE -> GF_CALL_ICMP6_TIME_EXCEEDED
+ *   pipeline records GF_PIPE_F_RESPONDER (GF_NETDEV_F_HANDLE_NS) -> the record's pad0: GF_CALL_ICMP6_NS /
+ *                                                           GF_CALL_ICMP6_ECHO_REPLY (the frame is not read)
  * nh_off is ETH_HLEN at every call site.  IPV4_GATEWAY and ROUTER_IP come from
  * gf_node_config; NODE_MAC from the program in slot lxc_id[i] of the responder's
  * cilium_policy array (gf_lxc_cfg.node_mac), or from gf_node_cfg.node_mac when the
