@@ -239,6 +239,47 @@ GF_HD uint32_t gf_pair_hash6(const uint32_t *a, const uint32_t *b) {
     return gf_hash_words(w, 8, 32);
 }
 
+// Flow-group bucket key of one classify call: the family bit on top of bits-1
+// bits of the group hash.  The width follows the batch size (gf_key_bits), so it
+// is computed on the host per call and passed by value to every kernel that
+// builds a key or takes one apart (uniform: it stays in scalar registers).
+struct gf_key_cfg {
+    uint32_t bits;         // sort key width (radix_sort_pairs' end_bit)
+    uint32_t fam;          // 1 << (bits - 1): the family of the CT path (1: IPv6 reaching conntrack)
+    uint32_t hash;         // fam - 1: the group-hash bits; all ones is the skip key (gf_key_skip)
+};
+#ifndef GF_KEY_BITS
+#define GF_KEY_BITS 0      // 0: by the batch size; 2..32 forces one width for every call (A/B builds)
+#endif
+#ifndef GF_SORT_RADIX
+#define GF_SORT_RADIX 9    // digit bits of the onesweep passes
+#endif
+// The one width rule of pack and schedule.  Sharing a bucket is always exact (a
+// bucket is serialized as a whole), so the key only has to keep sharing rare:
+// three bits past the batch size, rounded up to whole radix passes (every bit a
+// pass sorts is free), at most four passes.  At most n / 2^(bits - 1) of the
+// groups share a bucket.  9-bit digits: n <= 2^6 sorts 9 bits in one pass,
+// n <= 2^15 18 bits in two, n <= 2^24 27 bits in three, larger batches 32 bits
+// in four.
+// wide: the frame entry points (gf_pipeline_classify, gf_overlay_classify,
+// gf_host_classify) skip the three-pass tier: above 2^15 frames they keep the
+// full 32-bit key, because their handle_policy pass loses to a 27-bit key what
+// the sort gains.  A 32-bit key is sorted with
+// rocPRIM's default 8-bit digits (schedule_groups), as before the rule.
+inline uint32_t gf_key_bits(uint32_t n, bool wide = false) {
+    if (GF_KEY_BITS) return GF_KEY_BITS;
+    uint32_t lg = 1;
+    while (lg < 32 && (1ull << lg) < n) lg++;           // ceil_log2(max(n, 2))
+    uint32_t passes = (lg + 3 + GF_SORT_RADIX - 1) / GF_SORT_RADIX;
+    if (passes > 4 || (wide && passes > 2)) passes = 4;
+    const uint32_t bits = GF_SORT_RADIX * passes;
+    return bits < 32 ? bits : 32;
+}
+inline gf_key_cfg gf_key_for(uint32_t n, bool wide = false) {
+    const uint32_t bits = gf_key_bits(n, wide), fam = 1u << (bits - 1);
+    return gf_key_cfg{bits, fam, fam - 1u};
+}
+
 // Packed per-packet record used by the ingress kernel after grouping
 // (32 B, one dwordx4 x2 load).  cls: bits0-1 L3 class (0 other, 1 v4, 2 v6),
 // bit 2 TC_INDEX_F_SKIP_PROXY, bit 3 the pipeline packet ended before the tail

@@ -36,17 +36,18 @@ using namespace gfd;
 #define GF_DIAG 0      // diagnostic ablations (tools/diag.sh); 0 in the product build
 #endif
 // Tuning knobs of the flow-group kernel (tools/variants.sh sweeps them).
-#ifndef GF_KEY_BITS
-#define GF_KEY_BITS 32      // bucket key: family bit + (GF_KEY_BITS-1) bits of the group hash
-#endif
-#define GF_KEY_FAM (1u << (GF_KEY_BITS - 1))
-#define GF_KEY_HASH (GF_KEY_FAM - 1u)
+// The bucket key (gf_key_cfg, gf_common.h: family bit + bits-1 bits of the group
+// hash; GF_KEY_BITS forces a width, GF_SORT_RADIX sets the digit).
 // The key of every packet the handle_policy pass skips (a pipeline packet that
 // ended before the tail call, an egress packet that was not delivered locally):
 // they sort into one run, which the bucket schedule leaves out, so no lane reads
 // their records.  Group keys never take this value (gf_key_live).
-#define GF_KEY_SKIP GF_KEY_HASH
-__device__ __forceinline__ uint32_t gf_key_live(uint32_t k) { return (k & GF_KEY_HASH) == GF_KEY_SKIP ? k - 1u : k; }
+__device__ __forceinline__ uint32_t gf_key_skip(const gf_key_cfg &K) { return K.hash; }
+// h: a group hash (any 32 bits) -> its live family-0 key
+__device__ __forceinline__ uint32_t gf_key_live(uint32_t h, const gf_key_cfg &K) {
+    const uint32_t k = h & K.hash;
+    return k == K.hash ? k - 1u : k;
+}
 #ifndef GF_ING_MINW
 #define GF_ING_MINW 4       // __launch_bounds__ min waves per SIMD (register budget)
 #endif
@@ -1843,7 +1844,7 @@ __device__ __forceinline__ gf_ingress_out handle_policy(const IngCtx &X, const g
 // The 32-B record handle_policy reads and the packet's flow-group bucket key.
 // Only packets that can reach conntrack (an IP header is present) are bound to
 // their flow group; the rest carry no ordering constraint and are spread out.
-// GF_KEY_BITS-1 bits of the group hash are the sort key: groups that collide
+// K.bits-1 bits of the group hash are the sort key (gf_key_bits): groups that collide
 // share a bucket (always safe: a bucket is serialized as a whole), and a
 // shorter key is one radix pass less.  The top key bit is the family of the CT
 // path (1: IPv6 reaching conntrack).  skipped: a pipeline packet that ended
@@ -1851,7 +1852,8 @@ __device__ __forceinline__ gf_ingress_out handle_policy(const IngCtx &X, const g
 __device__ __forceinline__ uint32_t pack_rec(uint32_t i, uint32_t et, uint32_t len, uint32_t sa, uint32_t da,
                                              uint32_t w0, uint32_t w3, int l4, uint32_t proto, uint32_t sid,
                                              uint32_t ifx, uint16_t ep, uint32_t tci, bool skipped, bool have6,
-                                             const uint32_t *s6, const uint32_t *d6, gf_rec &r) {
+                                             const uint32_t *s6, const uint32_t *d6, gf_rec &r,
+                                             const gf_key_cfg &K) {
     r.len = len;
     r.saddr = sa; r.daddr = da;
     r.l4w0 = w0; r.l4w3 = (uint16_t)w3;
@@ -1864,15 +1866,15 @@ __device__ __forceinline__ uint32_t pack_rec(uint32_t i, uint32_t et, uint32_t l
     if (tci & 1) cls |= 4u;
     if (skipped) cls |= 8u;
     r.cls = (uint8_t)cls;
-    if (skipped) return GF_KEY_SKIP;
+    if (skipped) return gf_key_skip(K);
     const bool ct_ok = ((cls & 3) == 1 && len >= 34) || ((cls & 3) == 2 && len >= 54 && have6);
-    if (!ct_ok) return gf_key_live(gf_hash_words(&i, 1, 4) & GF_KEY_HASH);
-    if ((cls & 3) == 2) return gf_key_live(gf_pair_hash6(s6, d6) & GF_KEY_HASH) | GF_KEY_FAM;
-    return gf_key_live(gf_pair_hash4(sa, da) & GF_KEY_HASH);
+    if (!ct_ok) return gf_key_live(gf_hash_words(&i, 1, 4), K);
+    if ((cls & 3) == 2) return gf_key_live(gf_pair_hash6(s6, d6), K) | K.fam;
+    return gf_key_live(gf_pair_hash4(sa, da), K);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_ing_pack(gf_pkt_cols c, const uint16_t *slot_of, gf_rec *rec,
-                                                    uint32_t *keys) {
+                                                    uint32_t *keys, gf_key_cfg K) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= c.n) return;
     const uint32_t et = c.ethertype[i], len = c.len[i];
@@ -1887,11 +1889,11 @@ __global__ __launch_bounds__(BLOCK) void k_ing_pack(gf_pkt_cols c, const uint16_
     keys[i] = pack_rec(i, et, len, c.saddr4[i], c.daddr4[i], c.l4w0[i], c.l4w3[i], c.l4_off[i], c.proto[i],
                        c.src_identity ? c.src_identity[i] : 0u, c.ifindex ? c.ifindex[i] : 0u,
                        slot_of[c.lxc_id ? c.lxc_id[i] : 0], c.tc_index ? c.tc_index[i] : 0u, false,
-                       c.saddr6 != nullptr, s6, d6, r);
+                       c.saddr6 != nullptr, s6, d6, r, K);
     rec[i] = r;
 }
 
-// Flow-group schedule.  A bucket is a run of equal 32-bit group hash in the
+// Flow-group schedule.  A bucket is a run of equal bucket keys (gf_key_cfg) in the
 // stably sorted batch, so it holds whole flow groups with their packets in batch
 // order.  One lane runs one bucket to completion, packet after packet — the
 // order BPF would see them on one CPU — while different buckets (disjoint CT
@@ -1966,10 +1968,11 @@ __device__ __forceinline__ void flush_added(const IngCtx &X, uint32_t fam_bit, i
 // b mod GF_NCLS — the XCD the workgroup runs on, dispatch being round-robin over the
 // 8 XCDs — and move to the other classes' lists when theirs is drained, so that an
 // XCD's L2 would hold the policy maps of its class of endpoints only.  Measured with
-// 8 classes: k_ing_groups 2.90 vs 2.40 ms on config 2 — most likely because a
-// wave's 64 buckets are no longer neighbours in key order, so their CT home lines
-// (placed by the same pair hash) no longer share pages — so one class (the plain
-// longest-first list) stays.
+// 8 classes: k_ing_groups 2.90 vs 2.40 ms on config 2; the cause is not pinned
+// down.  (Not CT locality: a CT home line is placed by gf_key_hash / GF_HASH_CT
+// over the whole tuple, ports included, which is unrelated to the bucket key's
+// gf_pair_hash4, so neighbours in key order never shared CT pages.)  One class
+// (the plain longest-first list) stays.
 #ifndef GF_NCLS
 #define GF_NCLS 1u
 #endif
@@ -1989,8 +1992,9 @@ __device__ __forceinline__ void flush_added(const IngCtx &X, uint32_t fam_bit, i
 #define GF_SCHED_WORDS (3 * GF_NL * (GF_LCAP + 1) + 1 + GF_NL + 2 + 2 * GF_NL)
 #define GF_SCHED_HBYTES (GF_NL * (GF_LCAP + 1) * 4)    // the block-local bins of k_bucket_hist / order (dynamic LDS)
 // The list of a bucket: family from its key, class from its first packet's record.
-__device__ __forceinline__ uint32_t sched_list(uint32_t key, const gf_rec *rec, const uint32_t *perm, uint32_t b) {
-    const uint32_t f = key >> (GF_KEY_BITS - 1);
+__device__ __forceinline__ uint32_t sched_list(uint32_t key, const gf_rec *rec, const uint32_t *perm, uint32_t b,
+                                               const gf_key_cfg &K) {
+    const uint32_t f = key >> (K.bits - 1);
     const uint32_t x = rec ? (uint32_t)rec[perm[b]].ep % GF_NCLS : 0u;
     return f * GF_NCLS + x;
 }
@@ -2191,11 +2195,11 @@ __device__ __forceinline__ gf_ingress_out handle_policy_noct(const IngCtx &X, co
 // A mixed array: the packets of programs without conntrack leave the flow-group
 // sort's live range (the grouped kernels never see them).
 __global__ __launch_bounds__(BLOCK) void k_ing_noct_mark(uint32_t n, const gf_rec *rec, const gf_lxc_dev *cfgs,
-                                                         uint32_t *keys) {
+                                                         uint32_t *keys, gf_key_cfg K) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t ep = rec[i].ep;
-    if (ep && (cfgs[ep - 1].flags & GF_LXC_F_NO_CONNTRACK)) keys[i] = GF_KEY_SKIP;
+    if (ep && (cfgs[ep - 1].flags & GF_LXC_F_NO_CONNTRACK)) keys[i] = gf_key_skip(K);
 }
 // One thread per packet in batch order: coalesced record reads and out[i] (or pipeline
 // record, X.pout) writes, the
@@ -2248,13 +2252,14 @@ __global__ __launch_bounds__(BLOCK) void k_ing_noct(IngCtx X, uint32_t n, uint32
 }
 
 #define GF_LCAP 1024u
-// Bucket-size histogram per family (bit 31 of the bucket's sorted key):
+// Bucket-size histogram per family (the top bit of the bucket's sorted key, K.fam):
 // block-local LDS bins, one global add per non-empty bin.
 #define GF_SCHED_ITEMS 4096
 // off[q]: the start of run q in the sorted keys (nruns of them); its length is
 // the distance to the next start (or to n).
 __global__ __launch_bounds__(BLOCK) void k_bucket_hist(uint32_t n, const uint32_t *off, const uint32_t *skeys,
-                                                       const gf_rec *rec, const uint32_t *perm, uint32_t *sched) {
+                                                       const gf_rec *rec, const uint32_t *perm, uint32_t *sched,
+                                                       gf_key_cfg K) {
     extern __shared__ uint32_t h[];                     // GF_SCHED_HBYTES
     for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x) h[k] = 0;
     __syncthreads();
@@ -2263,8 +2268,8 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_hist(uint32_t n, const uint32_
     for (uint32_t q = b0 + threadIdx.x; q < b0 + GF_SCHED_ITEMS && q < nq; q += blockDim.x) {
         const uint32_t key = skeys[off[q]];
         uint32_t c = (q + 1 < nq ? off[q + 1] : n) - off[q];
-        if (c && key != GF_KEY_SKIP)
-            atomicAdd(&h[sched_list(key, rec, perm, off[q]) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
+        if (c && key != gf_key_skip(K))
+            atomicAdd(&h[sched_list(key, rec, perm, off[q], K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
     }
     __syncthreads();
     uint32_t *hist = GF_SCHED_HIST(sched);
@@ -2315,7 +2320,7 @@ __global__ __launch_bounds__(GF_LCAP) void k_bucket_base(uint32_t *sched) {
 // counts per bin, one global reservation per (block, bin).
 __global__ __launch_bounds__(BLOCK) void k_bucket_order(uint32_t n, const uint32_t *off, const uint32_t *skeys,
                                                         const gf_rec *rec, const uint32_t *perm, uint32_t *sched,
-                                                        uint2 *order, uint32_t skip1) {
+                                                        uint2 *order, uint32_t skip1, gf_key_cfg K) {
     extern __shared__ uint32_t h[];                     // GF_SCHED_HBYTES
     for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x) h[k] = 0;
     __syncthreads();
@@ -2326,8 +2331,8 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_order(uint32_t n, const uint32
     for (uint32_t q = b0 + threadIdx.x; q < b0 + GF_SCHED_ITEMS && q < nq; q += blockDim.x) {
         const uint32_t key = skeys[off[q]];
         uint32_t c = (q + 1 < nq ? off[q + 1] : n) - off[q];
-        if (c && key != GF_KEY_SKIP && !(skip1 && c == 1))
-            atomicAdd(&h[sched_list(key, rec, perm, off[q]) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
+        if (c && key != gf_key_skip(K) && !(skip1 && c == 1))
+            atomicAdd(&h[sched_list(key, rec, perm, off[q], K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
     }
     __syncthreads();
     for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x)
@@ -2336,8 +2341,8 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_order(uint32_t n, const uint32
     for (uint32_t q = b0 + threadIdx.x; q < b0 + GF_SCHED_ITEMS && q < nq; q += blockDim.x) {
         const uint32_t key = skeys[off[q]];
         uint32_t c = (q + 1 < nq ? off[q + 1] : n) - off[q];
-        if (c && key != GF_KEY_SKIP && !(skip1 && c == 1))
-            order[atomicAdd(&h[sched_list(key, rec, perm, off[q]) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u)] =
+        if (c && key != gf_key_skip(K) && !(skip1 && c == 1))
+            order[atomicAdd(&h[sched_list(key, rec, perm, off[q], K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u)] =
                 make_uint2(off[q], c);
     }
 }
@@ -2349,12 +2354,13 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_order(uint32_t n, const uint32
 // 0 = not a single-packet bucket); k_single_count / k_run_scan / k_single_write
 // rank them per family in index order.
 __global__ __launch_bounds__(BLOCK) void k_single_mark(uint32_t n, const uint32_t *off, const uint32_t *skeys,
-                                                       const uint32_t *perm, const uint32_t *sched, uint32_t *sw) {
+                                                       const uint32_t *perm, const uint32_t *sched, uint32_t *sw,
+                                                       gf_key_cfg K) {
     const uint32_t nq = *GF_SCHED_NRUNS(sched);
     for (uint32_t q = blockIdx.x * BLOCK + threadIdx.x; q < nq; q += gridDim.x * BLOCK) {
         const uint32_t b = off[q], key = skeys[b];
-        if ((q + 1 < nq ? off[q + 1] : n) - b != 1u || key == GF_KEY_SKIP) continue;
-        sw[perm[b]] = ((b + 1u) << 1) | (key >> (GF_KEY_BITS - 1));
+        if ((q + 1 < nq ? off[q + 1] : n) - b != 1u || key == gf_key_skip(K)) continue;
+        sw[perm[b]] = ((b + 1u) << 1) | (key >> (K.bits - 1));
     }
 }
 // the family of a packet's single-bucket word: 1 / 2, 0 = none
@@ -2543,7 +2549,7 @@ template <int NT>
 __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
                                                       PipeDev P, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
                                                       uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                      uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats) {
+                                                      uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
     extern __shared__ uint4 lds_rows[];
     uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
     __shared__ uint32_t sl[272];
@@ -2640,7 +2646,7 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
             PktHdr h2;
             parse_row(w.p, cap, len, h2);
             key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx, slot_of[lxc & 0xffffu],
-                           tci, false, true, h2.s6, h2.d6, rr);
+                           tci, false, true, h2.s6, h2.d6, rr, K);
             // the front's record flags (every GF_PIPE_F_* bit: the top three of the byte)
             // ride along in cls bits 4-6 for k_ing_groups' write-only completion (IngCtx::pout_wo)
             static_assert(((GF_PIPE_F_ICMP6_TE | GF_PIPE_F_LB | GF_PIPE_F_PORTMAP) & ~0xE0u) == 0,
@@ -2651,7 +2657,7 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
                 reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
             }
         } else {
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr);
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
         }
         rec[i] = rr;
         keys[i] = key;
@@ -2751,7 +2757,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *tunnel_id, const uint8_t *tc_index,
                                                   OvlDev O, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
                                                   uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                  uint8_t *snap_out, unsigned long long *stats) {
+                                                  uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
     extern __shared__ uint4 lds_rows[];
     uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
     __shared__ uint32_t sl[272];
@@ -2812,14 +2818,14 @@ __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *
             PktHdr h2;
             parse_row(w.p, cap, len, h2);
             key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, tunnel_id[i], ifx,
-                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr);
+                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr, K);
             rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);   // the front's flags for IngCtx::pout_wo, as k_pipe_front
             if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
                 reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
                 reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
             }
         } else {
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr);
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
         }
         rec[i] = rr;
         keys[i] = key;
@@ -3025,7 +3031,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_host_front(gf_frames fr, const uint32_t *mark, const uint8_t *tc_index,
                                                    HostDev H, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
                                                    uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                   uint8_t *snap_out, unsigned long long *stats) {
+                                                   uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
     extern __shared__ uint4 lds_rows[];
     uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
     __shared__ uint32_t sl[272];
@@ -3088,14 +3094,14 @@ __global__ __launch_bounds__(NT) void k_host_front(gf_frames fr, const uint32_t 
             PktHdr h2;
             parse_row(w.p, cap, len, h2);
             key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx,
-                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr);
+                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr, K);
             if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
                 reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
                 reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
             }
         } else {
             // an encap redirect keeps its secctx in the (skipped) record: TRACE_TO_OVERLAY's label
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, r == HO_ENCAP ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr);
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, r == HO_ENCAP ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
         }
         rec[i] = rr;
         keys[i] = key;
@@ -3205,7 +3211,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
                                                  PipeDev P, NdxDev X, const uint16_t *slot_of, gf_rec *rec,
                                                  uint32_t *keys, uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                 uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats) {
+                                                 uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
     extern __shared__ uint4 lds_rows[];
     uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
     __shared__ uint32_t sl[272];
@@ -3307,7 +3313,7 @@ __global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc
             PktHdr h2;
             parse_row(w.p, cap, len, h2);
             key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx, slot_of[lxc & 0xffffu],
-                           tci, false, true, h2.s6, h2.d6, rr);
+                           tci, false, true, h2.s6, h2.d6, rr, K);
             rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);   // the front's flags for IngCtx::pout_wo, as k_pipe_front
             if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
                 reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
@@ -3315,7 +3321,7 @@ __global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc
             }
         } else {
             // an encap redirect keeps its secctx in the (skipped) record: TRACE_TO_OVERLAY's label
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, enc ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr);
+            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, enc ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
         }
         rec[i] = rr;
         keys[i] = key;
@@ -4446,6 +4452,7 @@ struct EgDev {
     const gf_lxc_dev *cfgs;
     uint8_t *v6blk;                     // per front block: holds an IPv6 frame (k_eg_front<4> writes, <6> reads), or null
     const uint16_t *slot_of;
+    gf_key_cfg K;                       // the call's bucket key (gf_key_for(n))
     gf_htab_desc ct4, ct6, lxc, tunnel;
     const uint32_t *lxset, *tnset;      // cilium_lxc's / the tunnel map's IPv4 keys: address set + slots
     uint32_t lxbits, lxzero, tnbits, tnzero;   // (Map::addr_set), or null
@@ -4897,20 +4904,20 @@ __global__ __launch_bounds__(BLOCK) void k_eg_front(gf_frames fr, const uint16_t
         if (r.st == 0 && FAM == 6) {
             uint32_t s6[4], d6[4];
             for (int k = 0; k < 4; k++) { s6[k] = wg.r32(22 + 4 * k); d6[k] = wg.r32(38 + 4 * k); }
-            key = gf_key_live(gf_pair_hash6(s6, d6) & GF_KEY_HASH) | GF_KEY_FAM;   // the IPv6 family of the schedule
+            key = gf_key_live(gf_pair_hash6(s6, d6), E.K) | E.K.fam;   // the IPv6 family of the schedule
         } else if (r.st == 0) {
-            key = gf_key_live(gf_pair_hash4(r.t_saddr, r.t_daddr) & GF_KEY_HASH);
+            key = gf_key_live(gf_pair_hash4(r.t_saddr, r.t_daddr), E.K);
             if (E.conn) {
                 E.keysP[i] = key;
                 const bool tu = (r.nh == 6 || r.nh == 17) && skb_ok(r.l4_off, 4, len);
                 const uint32_t sp = tu ? w.r16((uint32_t)r.l4_off) : 0u, dp = tu ? w.r16((uint32_t)r.l4_off + 2u) : 0u;
-                key = gf_key_live(gf_conn_hash4(r.t_saddr, sp, r.t_daddr, dp, r.nh) & GF_KEY_HASH);
+                key = gf_key_live(gf_conn_hash4(r.t_saddr, sp, r.t_daddr, dp, r.nh), E.K);
                 if (r.nh == 1) atomicOr(E.cflag, 1u);
             }
             const uint32_t lo = E.loopback;
             if (r.t_saddr == r.t_daddr || (lo && (r.t_saddr == lo || r.t_daddr == lo)) || (E.strict & 1u)) *E.seq = 1u;
         } else {
-            key = GF_KEY_SKIP;                        // final in the front: k_eg_groups has nothing to do
+            key = gf_key_skip(E.K);                   // final in the front: k_eg_groups has nothing to do
             if (E.conn) E.keysP[i] = key;
             if (o.stage == GF_STAGE_FROM_LXC) {
                 if (ret < 0 || ret == TC_SHOT) {
@@ -4926,7 +4933,7 @@ __global__ __launch_bounds__(BLOCK) void k_eg_front(gf_frames fr, const uint16_t
         keys[i] = key;
         {                                                     // not (yet) a local delivery: skipped by the
             gf_rec rr;                                        // handle_policy pass (coalesced writes here,
-            const uint32_t k2 = pack_rec(i, 0, len, 0, 0, 0, 0, 0, 0, 0, 0, r.ep, 0, true, false, nullptr, nullptr, rr);
+            const uint32_t k2 = pack_rec(i, 0, len, 0, 0, 0, 0, 0, 0, 0, 0, r.ep, 0, true, false, nullptr, nullptr, rr, E.K);
             E.rec2[i] = rr;                                   // none for most packets in k_eg_groups)
             E.key2[i] = k2;
             if (E.conn) E.key2P[i] = k2;
@@ -4951,12 +4958,13 @@ __global__ __launch_bounds__(BLOCK) void k_eg_pick_keys(const uint32_t *cflag, c
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) keys[i] = key2P[i];
 }
 __global__ __launch_bounds__(BLOCK) void k_eg_seq_keys(const uint32_t *seq, const uint32_t *cflag,
-                                                       const uint32_t *keysP, uint32_t n, uint32_t *keys) {
+                                                       const uint32_t *keysP, uint32_t n, uint32_t *keys,
+                                                       gf_key_cfg K) {
     if (*seq) {
-        for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) keys[i] &= GF_KEY_FAM;
+        for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) keys[i] &= K.fam;
     } else if (cflag && *cflag) {
         for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-            if (!(keys[i] & GF_KEY_FAM)) keys[i] = keysP[i];
+            if (!(keys[i] & K.fam)) keys[i] = keysP[i];
     }
 }
 
@@ -5673,13 +5681,13 @@ __global__ __launch_bounds__(BLOCK, GF_EG_MINW) void k_eg_groups(EgDev E, uint32
                 const gf_lxc_dev *c = E.cfgs + (r.ep - 1);
                 uint32_t kk = pack_rec(i, h2.et, r.len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto,
                                        gload<uint32_t>(&c->seclabel), ifx, E.slot_of[lxc & 0xffffu], 0, false, true,
-                                       h2.s6, h2.d6, rr);
+                                       h2.s6, h2.d6, rr, E.K);
                 if (E.conn) {                           // the delivery's connection (handle_policy's CT tuple)
                     E.key2P[i] = kk;
                     if (h2.et == 0x0800 && r.len >= 34) {
                         const bool tu = h2.proto == 6 || h2.proto == 17;
                         kk = gf_key_live(gf_conn_hash4(h2.sa, tu ? (h2.w0 & 0xffffu) : 0u, h2.da, tu ? (h2.w0 >> 16) : 0u,
-                                                       h2.proto) & GF_KEY_HASH);
+                                                       h2.proto), E.K);
                     }
                 }
                 key2[i] = kk;
@@ -6430,14 +6438,12 @@ static int ws_grow(uint32_t n) {
     return 0;
 }
 
-// The flow-group schedule of ws().keys[0..n): stable radix sort of (32-bit group
-// hash, index), the start of every run of equal hashes (one bucket per run: a
+// The flow-group schedule of ws().keys[0..n): stable radix sort of (bucket key of
+// gf_key_for(n) bits, index), the start of every run of equal hashes (one bucket per run: a
 // select of the positions whose key differs from the one before), then the
 // longest-first bucket order per family, built on the device (no host round
 // trip): ws().perm / order / sched.
-#ifndef GF_SORT_RADIX
-#define GF_SORT_RADIX 8                // digit bits of the onesweep passes (rocPRIM's gfx950 default)
-#endif
+// GF_SORT_RADIX (gf_common.h): digit bits of the onesweep passes; 8 is rocPRIM's gfx950 default
 #ifndef GF_SORT_IPT
 #define GF_SORT_IPT 16
 #endif
@@ -6449,6 +6455,15 @@ using GfSortCfg = rocprim::radix_sort_config<
     rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, GF_SORT_IPT>, rocprim::kernel_config<1024, GF_SORT_IPT>,
                                         GF_SORT_RADIX, rocprim::block_radix_rank_algorithm::match>>;
 #endif
+// The schedule's sort of (key, index): GfSortCfg's digits below 32 key bits; a 32-bit
+// key takes rocPRIM's default config (four 8-bit passes are cheaper than 9/9/9/5).
+static hipError_t sort_keys(void *tmp, size_t &bytes, const uint32_t *keys, uint32_t *skeys, uint32_t *perm, uint32_t n,
+                            uint32_t bits, hipStream_t s) {
+    const rocprim::counting_iterator<uint32_t> idx(0u);
+    if (bits == 32 && !GF_KEY_BITS)
+        return rocprim::radix_sort_pairs<rocprim::default_config>(tmp, bytes, keys, skeys, idx, perm, n, 0, bits, s);
+    return rocprim::radix_sort_pairs<GfSortCfg>(tmp, bytes, keys, skeys, idx, perm, n, 0, bits, s);
+}
 // Run starts of the sorted keys in three passes over GF_RUN_ITEMS-key tiles:
 // count the starts per tile, scan the tile counts (one block), write each
 // tile's starts at its offset in position order (wave ballots + LDS scan).
@@ -6521,15 +6536,17 @@ __global__ __launch_bounds__(BLOCK) void k_run_write(uint32_t n, const uint32_t 
 // rec: the packets' handle_policy records (the bucket's endpoint class), or null
 // (every bucket in class 0: the egress from-container pass).
 // single: single-packet buckets in packet-index order (the egress passes).
-static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullptr, bool single = false) {
+// wide: the keys came from a frame front (gf_key_for(n, true)).
+static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullptr, bool single = false,
+                           bool wide = false) {
     Workspace &w = ws();
+    const gf_key_cfg K = gf_key_for(n, wide);           // the width the keys were built with: the same rule, the same n
     auto grow = [](DevBuf &b, size_t want) -> int { return b.bytes >= want ? 0 : b.ensure(want); };
     int r;
     uint32_t *d_sched = (uint32_t *)w.sched.p, *d_nruns = GF_SCHED_NRUNS(d_sched);
     size_t sort_bytes = 0;
-    (void)rocprim::radix_sort_pairs<GfSortCfg>(nullptr, sort_bytes, (uint32_t *)w.keys.p, (uint32_t *)w.skeys.p,
-                                               rocprim::counting_iterator<uint32_t>(0u), (uint32_t *)w.perm.p, n, 0,
-                                               GF_KEY_BITS, s);
+    (void)sort_keys(nullptr, sort_bytes, (const uint32_t *)w.keys.p, (uint32_t *)w.skeys.p, (uint32_t *)w.perm.p, n,
+                    K.bits, s);
     const uint32_t nt = (n + GF_RUN_ITEMS - 1) / GF_RUN_ITEMS;
     if ((r = grow(w.tmp, sort_bytes + 256)) || (r = grow(w.tcnt, (size_t)nt * 4 + 16))) return r;
     single = single && GF_SINGLE_ORDER && GF_NCLS == 1;
@@ -6539,9 +6556,8 @@ static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullpt
     size_t tb = w.tmp.bytes;
     {
         ProfScope ps("rocprim_radix_sort", s);
-        if (hip_ok(rocprim::radix_sort_pairs<GfSortCfg>(w.tmp.p, tb, (uint32_t *)w.keys.p, (uint32_t *)w.skeys.p,
-                                                        rocprim::counting_iterator<uint32_t>(0u), (uint32_t *)w.perm.p,
-                                                        n, 0, GF_KEY_BITS, s), "radix_sort_pairs"))
+        if (hip_ok(sort_keys(w.tmp.p, tb, (const uint32_t *)w.keys.p, (uint32_t *)w.skeys.p, (uint32_t *)w.perm.p, n,
+                             K.bits, s), "radix_sort_pairs"))
             return -EIO;
     }
     {
@@ -6566,15 +6582,15 @@ static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullpt
         uint32_t g = (n + GF_SCHED_ITEMS - 1) / GF_SCHED_ITEMS;
         const gf_rec *lrec = GF_NCLS > 1 ? rec : nullptr;
         hipLaunchKernelGGL(k_bucket_hist, dim3(g), dim3(BLOCK), GF_SCHED_HBYTES, s, n, (const uint32_t *)w.off.p,
-                           (const uint32_t *)w.skeys.p, lrec, (const uint32_t *)w.perm.p, d_sched);
+                           (const uint32_t *)w.skeys.p, lrec, (const uint32_t *)w.perm.p, d_sched, K);
         hipLaunchKernelGGL(k_bucket_base, dim3(1), dim3(GF_LCAP), 0, s, d_sched);
         hipLaunchKernelGGL(k_bucket_order, dim3(g), dim3(BLOCK), GF_SCHED_HBYTES, s, n, (const uint32_t *)w.off.p,
                            (const uint32_t *)w.skeys.p, lrec, (const uint32_t *)w.perm.p, d_sched, (uint2 *)w.order.p,
-                           single ? 1u : 0u);
+                           single ? 1u : 0u, K);
         if (single) {                                   // (the words were cleared by k_run_count)
             hipLaunchKernelGGL(k_single_mark, dim3(std::min<uint32_t>((n + BLOCK - 1) / BLOCK, 8192u)), dim3(BLOCK), 0, s, n,
                                (const uint32_t *)w.off.p, (const uint32_t *)w.skeys.p, (const uint32_t *)w.perm.p,
-                               (const uint32_t *)d_sched, (uint32_t *)w.sb.p);
+                               (const uint32_t *)d_sched, (uint32_t *)w.sb.p, K);
             hipLaunchKernelGGL(k_single_count, dim3(nt), dim3(BLOCK), 0, s, n, (const uint32_t *)w.sb.p,
                                (uint32_t *)w.st0.p, (uint32_t *)w.st1.p);
             hipLaunchKernelGGL(k_run_scan, dim3(1), dim3(1024), 0, s, nt, (uint32_t *)w.st0.p, (uint32_t *)w.st0.p + nt,
@@ -7101,11 +7117,11 @@ static int lru_evict_maps(const std::vector<std::shared_ptr<Map>> &ms, uint32_t 
 }
 
 // A mixed array's packets of programs without conntrack out of the schedule (ws().keys).
-static int noct_mark(const std::shared_ptr<PolicyArray> &a, uint32_t n, hipStream_t s) {
+static int noct_mark(const std::shared_ptr<PolicyArray> &a, uint32_t n, hipStream_t s, bool wide = false) {
     Workspace &w = ws();
     ProfScope ps("k_ing_noct_mark", s);
     hipLaunchKernelGGL(k_ing_noct_mark, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, n, (const gf_rec *)w.rec.p,
-                       (const gf_lxc_dev *)a->d_cfgs.p, (uint32_t *)w.keys.p);
+                       (const gf_lxc_dev *)a->d_cfgs.p, (uint32_t *)w.keys.p, gf_key_for(n, wide));
     return hip_ok(hipGetLastError(), "k_ing_noct_mark");
 }
 
@@ -7160,14 +7176,15 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
         ProfScope ps("k_ing_pack", s);
         hipLaunchKernelGGL(k_ing_pack, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *pkts,
                            (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p,
-                           (uint32_t *)w.keys.p);
+                           (uint32_t *)w.keys.p, gf_key_for(n));
         if ((r = hip_ok(hipGetLastError(), "k_ing_pack"))) return r;
     }
     host_mark("pack");
     // Programs without conntrack: their packets leave the schedule (mixed array), or
     // there is no schedule at all (every program; k_ing_noct alone, below)
-    if (noct == 1 && !prepared && (r = noct_mark(a, n, s))) return r;
-    if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, ta && ta->kind == 2))) return r;
+    const bool wide = ta && ta->kind == 1;              // the frame fronts' keys (gf_key_for(n, true))
+    if (noct == 1 && !prepared && (r = noct_mark(a, n, s, wide))) return r;
+    if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, ta && ta->kind == 2, wide))) return r;
     host_mark("sched");
     uint32_t *d_sched = (uint32_t *)w.sched.p;
     // 4. handle_policy: one bucket per lane, buckets from the longest-first queue
@@ -7277,7 +7294,8 @@ static int ingress_prepare(const std::shared_ptr<PolicyArray> &a, const gf_pkt_c
     {
         ProfScope ps("k_ing_pack", s);
         hipLaunchKernelGGL(k_ing_pack, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *pkts,
-                           (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p);
+                           (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p,
+                           gf_key_for(n));
         if ((r = hip_ok(hipGetLastError(), "k_ing_pack"))) return r;
     }
     const int noct = array_noct(a);
@@ -7510,19 +7528,19 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
             ProfScope ps("k_nd_front", s);
             if (nt == 256)
                 hipLaunchKernelGGL(k_nd_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tc_index, b->flow_hash, P, X,
-                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
+                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
             else
                 hipLaunchKernelGGL(k_nd_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tc_index, b->flow_hash, P, X,
-                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
+                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
             return hip_ok(hipGetLastError(), "k_nd_front");
         }
         ProfScope ps("k_pipe_front", s);
         if (nt == 256)
             hipLaunchKernelGGL(k_pipe_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tc_index, b->flow_hash, P,
-                               slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
+                               slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
         else
             hipLaunchKernelGGL(k_pipe_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tc_index, b->flow_hash, P,
-                               slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink);
+                               slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
         return hip_ok(hipGetLastError(), "k_pipe_front");
     };
     c2.flow_hash = b->flow_hash;
@@ -7599,10 +7617,10 @@ int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf
         ProfScope ps("k_ovl_front", s);
         if (nt == 256)
             hipLaunchKernelGGL(k_ovl_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
         else
             hipLaunchKernelGGL(k_ovl_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
         return hip_ok(hipGetLastError(), "k_ovl_front");
     };
     c2.flow_hash = b->flow_hash;
@@ -7694,10 +7712,10 @@ int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipe
         ProfScope ps("k_host_front", s);
         if (nt == 256)
             hipLaunchKernelGGL(k_host_front<256>, dim3(grid), dim3(256), lds, s, fr, b->mark, b->tc_index, H, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
         else
             hipLaunchKernelGGL(k_host_front<128>, dim3(grid), dim3(128), lds, s, fr, b->mark, b->tc_index, H, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink);
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
         return hip_ok(hipGetLastError(), "k_host_front");
     };
     c2.flow_hash = b->flow_hash;
@@ -8346,6 +8364,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     EgDev E{};
     E.cfgs = (const gf_lxc_dev *)a->d_cfgs.p;
     E.slot_of = (const uint16_t *)a->d_slot_of_lxc.p;
+    E.K = gf_key_for(n);
     E.ct4 = cfg_ct4; E.ct6 = cfg_ct6;
     if ((r = grow(ew.v6blk, (n + BLOCK - 1) / BLOCK))) return r;
     E.v6blk = GF_EG_LEAN ? (uint8_t *)ew.v6blk.p : nullptr;
@@ -8429,7 +8448,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
         hipLaunchKernelGGL(k_eg_front<6>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 16, s, fr, b->lxc_id, b->flow_hash,
                            E, (EgRec *)ew.erec.p, (uint32_t *)w.keys.p, out, fsink);
         hipLaunchKernelGGL(k_eg_seq_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint32_t *)ew.seq.p,
-                           (const uint32_t *)E.cflag, (const uint32_t *)E.keysP, n, (uint32_t *)w.keys.p);
+                           (const uint32_t *)E.cflag, (const uint32_t *)E.keysP, n, (uint32_t *)w.keys.p, E.K);
         if ((r = hip_ok(hipGetLastError(), "k_eg_front"))) return r;
     }
     if (check) {
