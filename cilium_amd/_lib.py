@@ -127,6 +127,12 @@ class gf_overlay_batch(C.Structure):
 GF_DROP_NON_LOCAL = 151
 GF_STAGE_OVERLAY = 6
 GF_OVERLAY_F_TRACE_NOTIFY = 1 << 0
+GF_OVERLAY_F_GENEVE = 1 << 1
+GF_DROP_NO_TUNNEL_OPT, GF_DROP_INVALID_GENEVE = 148, 149
+
+
+class gf_tunnel_opts(C.Structure):
+    _fields_ = [("opt", C.c_void_p), ("opt_stride", C.c_uint32), ("opt_len", C.c_void_p)]
 
 
 class gf_host_cfg(C.Structure):
@@ -205,6 +211,9 @@ _sig("gf_pipeline_classify", C.c_int, C.c_int, C.POINTER(gf_pipe_batch), C.c_uin
 _sig("gf_pipeline_classify_tunnel", C.c_int, C.c_int, C.POINTER(gf_pipe_batch), C.c_uint32, VP, VP, VP, VP, VP)
 _sig("gf_overlay_load", C.c_int, C.POINTER(gf_overlay_cfg))
 _sig("gf_overlay_classify", C.c_int, C.c_int, C.POINTER(gf_overlay_batch), C.c_uint32, VP, VP, VP)
+_sig("gf_overlay_classify_opts", C.c_int, C.c_int, C.POINTER(gf_overlay_batch), C.POINTER(gf_tunnel_opts), C.c_uint32,
+     VP, VP, VP)
+_sig("gf_lxc_egress_tunnel_meta", C.c_int, C.c_int, VP, VP, C.c_uint32, VP, VP, VP, VP)
 _sig("gf_host_load", C.c_int, C.POINTER(gf_host_cfg))
 _sig("gf_host_classify", C.c_int, C.c_int, C.POINTER(gf_host_batch), C.c_uint32, VP, VP, VP)
 _sig("gf_respond_load", C.c_int, C.POINTER(gf_respond_cfg))
@@ -243,7 +252,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_lxc_egress_classify", "gf_ct_gc", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

@@ -113,7 +113,7 @@ enum {
     D_POLICY = -133, D_INVALID = -134, D_CT_INVALID_HDR = -135, D_CT_UNKNOWN_PROTO = -137,
     D_UNKNOWN_L3 = -139, D_MISSED_TAIL_CALL = -140, D_WRITE_ERROR = -141, D_UNKNOWN_L4 = -142,
     D_CSUM_L4 = -154, D_CT_CREATE_FAILED = -155, D_NO_SERVICE = -158, D_POLICY_L4 = -159,
-    D_NON_LOCAL = -151,
+    D_NON_LOCAL = -151, D_NO_TUNNEL_OPT = -148, D_INVALID_GENEVE = -149,
 };
 enum { CT_NEW = 0, CT_ESTABLISHED = 1, CT_REPLY = 2, CT_RELATED = 3 };
 enum { ACT_UNSPEC = 0, ACT_CREATE = 1, ACT_CLOSE = 2 };
@@ -2687,7 +2687,18 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
 // program on the tunnel device.  Each frame is the inner frame; its
 // bpf_tunnel_key.tunnel_id (the sender's identity) comes as a column.  Not
 // modelled: skb_get_tunnel_key failing (DROP_NO_TUNNEL_KEY, it cannot fail for a
-// frame the tunnel device received) and Geneve options.
+// frame the tunnel device received).
+// ENCAP_GENEVE (GF_OVERLAY_F_GENEVE) is the GENEVE instance of the front: handle_ipv6's
+// block :54-67, skb_get_tunnel_opt + parse_geneve_options (lib/geneve.h:46-60), between
+// the length check and the endpoint lookup.  handle_ipv4 has no such block.  The lane's
+// options come as two columns (OvlOpt); only the first word of the 64-byte buffer is ever
+// looked at, so that is all the kernel loads.
+template <bool GENEVE> struct OvlOpt {};               // VXLAN: no kernel argument bytes beyond the empty struct
+template <> struct OvlOpt<true> {
+    const uint8_t *opt;            // n * stride, 4-byte aligned rows (gf_tunnel_opts)
+    const uint8_t *len;            // options_len per packet
+    uint32_t stride;
+};
 struct OvlDev {
     gf_htab_desc lxc;
     const uint32_t *lxset;         // cilium_lxc's IPv4 keys: address set + slots (Map::addr_set), or null
@@ -2699,8 +2710,11 @@ struct OvlDev {
 };
 enum { OV_TO_HOST = 1002 };
 
+// gw / gl (GENEVE): the first word of the lane's option buffer as skb_get_tunnel_opt leaves it
+// (bytes past options_len zero) and options_len.
+template <bool GENEVE>
 __device__ int ovl_program(const OvlDev &O, Row &w, const PktHdr &h, uint32_t et, uint32_t len, uint32_t &ifx,
-                           uint32_t &lxc, uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
+                           uint32_t &lxc, uint32_t &mapped, uint32_t &ndport, uint32_t &ab, uint32_t gw, uint32_t gl) {
     if (et == 0x0800) {
         if (len < 34) return D_INVALID;                 // revalidate_data (:114-115)
         uint32_t kw[5] = {w.r32(30), 0, 0, 0, 1u};      // lookup_ip4_endpoint (:123)
@@ -2726,6 +2740,13 @@ __device__ int ovl_program(const OvlDev &O, Row &w, const PktHdr &h, uint32_t et
     }
     if (et == 0x86DD) {
         if (len < 54) return D_INVALID;                 // :46-47
+        if constexpr (GENEVE) {
+            // bpf_skb_get_tunnel_opt (net/core/filter.c): -ENOENT without options, -ENOMEM past the buffer (:60-61)
+            if (gl == 0 || gl > 64) return D_NO_TUNNEL_OPT;
+            ab += 1 + 4;
+            // parse_geneve_options (:63-65): class 0xffff, type 1, (length & 0x1f) << 2 == 4; r1-r3 ignored
+            if ((gw & 0x1fffffffu) != 0x0101ffffu) return D_INVALID_GENEVE;
+        }
         uint32_t kw[5] = {w.r32(38), w.r32(42), w.r32(46), w.r32(50), 2u};   // lookup_ip6_endpoint (:70)
         const int64_t f = ht_find<20>(O.lxc, kw, key_hash<20>(kw));
         ab += 20 + 8;
@@ -2753,11 +2774,14 @@ __device__ int ovl_program(const OvlDev &O, Row &w, const PktHdr &h, uint32_t et
 // its frame in LDS (NT * snap_stride bytes of dynamic shared memory, <= 32 KiB:
 // five blocks per CU, so the kernel is not held to k_pipe_front's 64 VGPRs),
 // the handle_policy record and flow-group key written directly for ingress_run.
-template <int NT>
+// GENEVE: the lane's option word and options_len are two coalesced column loads issued
+// before the frame-row copy (registers, no LDS); the VXLAN instances compile without them.
+template <int NT, bool GENEVE>
 __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *tunnel_id, const uint8_t *tc_index,
                                                   OvlDev O, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
                                                   uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                  uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
+                                                  uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K,
+                                                  OvlOpt<GENEVE> G) {
     extern __shared__ uint4 lds_rows[];
     uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
     __shared__ uint32_t sl[272];
@@ -2767,6 +2791,15 @@ __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *
     const uint32_t b0 = blockIdx.x * NT;
     const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
     const size_t bytes = (size_t)nb * S;
+    uint32_t gw = 0, gl = 0;
+    if constexpr (GENEVE) {
+        if (b0 + threadIdx.x < fr.n) {
+            gl = G.len[b0 + threadIdx.x];
+            gw = *reinterpret_cast<const uint32_t *>(G.opt + (size_t)(b0 + threadIdx.x) * G.stride);
+            // the zero-initialised buffer past options_len (gl > 64 is refused before the word is looked at)
+            if (gl < 4) gw &= (1u << (8 * gl)) - 1u;
+        }
+    }
     {
         const uint8_t *src = fr.snap + (size_t)b0 * S;
         size_t k0 = 0;
@@ -2801,7 +2834,7 @@ __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *
                 for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
             }
         }
-        const int r = ovl_program(O, w, h, et, len, ifx, lxc, mapped, ndport, ab);
+        const int r = ovl_program<GENEVE>(O, w, h, et, len, ifx, lxc, mapped, ndport, ab, gw, gl);
         if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
         o.stage = GF_STAGE_OVERLAY;
         const bool tail = r == ND_TAILCALL;
@@ -2846,6 +2879,30 @@ __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *
         for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
     }
     if (stats) st.flush(stats);
+}
+
+// encap_and_redirect's bpf_tunnel_key.tunnel_id and GENEVE_OPTS (lib/encap.h:43, 53, 72-81) for
+// the records of a from-container call (gf_lxc_egress_tunnel_meta): one packet per lane, the
+// sender's program through the cilium_policy slot table as k_ing_pack reads it.
+__global__ __launch_bounds__(BLOCK) void k_tun_meta(const uint16_t *lxc_id, const gf_egress_out *recs, uint32_t n,
+                                                    const uint16_t *slot_of, const gf_lxc_dev *cfgs,
+                                                    uint32_t *tunnel_id, uint32_t *opt, uint8_t *opt_len) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t tid = 0, w0 = 0, w1 = 0, ol = 0;
+    if (recs[i].eg_flags & GF_EG_F_ENCAP) {
+        const uint32_t slot = slot_of[lxc_id[i]];
+        if (slot) {                                     // (an encap record always has a program)
+            tid = gload<uint32_t>(&cfgs[slot - 1].seclabel);
+            w0 = 0x0101ffffu;                           // ff ff 01 01: class, type, len >> 2
+            w1 = __builtin_bswap32(tid);                // the identity, big-endian
+            ol = 8;
+        }
+    }
+    tunnel_id[i] = tid;
+    opt[2 * (size_t)i] = w0;
+    opt[2 * (size_t)i + 1] = w1;
+    opt_len[i] = (uint8_t)ol;
 }
 
 // ================================================================ from-host
@@ -7564,18 +7621,28 @@ int gf_overlay_load(const gf_overlay_cfg *cfg) {
     return new_handle(p);
 }
 
-int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf_pipeline_out *out,
-                        uint8_t *snap_out, void *stream) {
+// gf_overlay_classify (with_opts false: a Geneve program is refused) and gf_overlay_classify_opts.
+static int overlay_call(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts *opts, bool with_opts,
+                        uint32_t now_sec, gf_pipeline_out *out, uint8_t *snap_out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
     auto o = get_obj(ovl);
     if (!o || o->kind != ObjKind::ProgOverlay) return -EBADF;
     auto p = std::static_pointer_cast<ProgOverlay>(o);
     if (!b) return -EFAULT;
+    const bool geneve = p->cfg.flags & GF_OVERLAY_F_GENEVE;
+    if (geneve && !with_opts) return -EINVAL;          // ENCAP_GENEVE reads options: gf_overlay_classify_opts
     const gf_frames &fr = b->frames;
     if (fr.n == 0) return 0;
     if (!fr.snap || !fr.len || !out || !b->tunnel_id) return -EFAULT;
     if (fr.snap_stride < 14 || fr.snap_stride > 256) return -EINVAL;   // a header snap, staged in LDS
     if (fr.n > (1u << 30)) return -E2BIG;
+    OvlOpt<true> G{};
+    if (geneve) {                                      // a VXLAN program ignores opts
+        if (!opts || !opts->opt || !opts->opt_len) return -EFAULT;
+        if (opts->opt_stride < 4 || opts->opt_stride > 64 || (opts->opt_stride & 3u) || ((uintptr_t)opts->opt & 3u))
+            return -EINVAL;
+        G.opt = opts->opt; G.len = opts->opt_len; G.stride = opts->opt_stride;
+    }
     hipStream_t s = (hipStream_t)stream;
     HostMarks hm;
     CtxScope cx(s);
@@ -7615,17 +7682,64 @@ int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf
     c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
     auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
         ProfScope ps("k_ovl_front", s);
-        if (nt == 256)
-            hipLaunchKernelGGL(k_ovl_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
+        if (geneve) {
+            if (nt == 256)
+                hipLaunchKernelGGL((k_ovl_front<256, true>), dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
+                                   rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true), G);
+            else
+                hipLaunchKernelGGL((k_ovl_front<128, true>), dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
+                                   rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true), G);
+        } else if (nt == 256)
+            hipLaunchKernelGGL((k_ovl_front<256, false>), dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true),
+                               OvlOpt<false>{});
         else
-            hipLaunchKernelGGL(k_ovl_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
+            hipLaunchKernelGGL((k_ovl_front<128, false>), dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
+                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true),
+                               OvlOpt<false>{});
         return hip_ok(hipGetLastError(), "k_ovl_front");
     };
     c2.flow_hash = b->flow_hash;
     return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
                        snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+}
+
+int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf_pipeline_out *out,
+                        uint8_t *snap_out, void *stream) {
+    return overlay_call(ovl, b, nullptr, false, now_sec, out, snap_out, stream);
+}
+
+int gf_overlay_classify_opts(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts *opts, uint32_t now_sec,
+                             gf_pipeline_out *out, uint8_t *snap_out, void *stream) {
+    return overlay_call(ovl, b, opts, true, now_sec, out, snap_out, stream);
+}
+
+// ---- encap_and_redirect's tunnel metadata of an egress call's records ----
+int gf_lxc_egress_tunnel_meta(int policy_array, const uint16_t *lxc_id, const gf_egress_out *records, uint32_t n,
+                              uint32_t *tunnel_id, uint8_t *opt, uint8_t *opt_len, void *stream) {
+    std::shared_lock<std::shared_mutex> g(prog_lock());
+    auto o = get_obj(policy_array);
+    if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
+    auto a = std::static_pointer_cast<PolicyArray>(o);
+    if (n == 0) return 0;
+    if (!lxc_id || !records || !tunnel_id || !opt || !opt_len) return -EFAULT;
+    if ((uintptr_t)opt & 3u) return -EINVAL;           // written as two words per packet (gf_tunnel_opts' alignment)
+    if (n > (1u << 30)) return -E2BIG;
+    hipStream_t s = (hipStream_t)stream;
+    CtxScope cx(s);
+    std::lock_guard<std::mutex> ag(a->mu);
+    MapLocks L;                                        // prog_table pushes the programs' maps
+    lock_array_maps(L, a);
+    L.lock();
+    CallOrder co(s, L, a.get());
+    int r;
+    std::vector<std::shared_ptr<ProgLxc>> progs;
+    if ((r = prog_table(a, s, progs))) return r;
+    ProfScope ps("k_tun_meta", s);
+    hipLaunchKernelGGL(k_tun_meta, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, lxc_id, records, n,
+                       (const uint16_t *)a->d_slot_of_lxc.p, (const gf_lxc_dev *)a->d_cfgs.p, tunnel_id,
+                       reinterpret_cast<uint32_t *>(opt), opt_len);
+    return hip_ok(hipGetLastError(), "k_tun_meta");
 }
 
 // ---- from-host ----

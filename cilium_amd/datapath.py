@@ -17,7 +17,7 @@ import numpy as np
 from . import bpf
 from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
-                   gf_overlay_batch, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
+                   gf_overlay_batch, gf_tunnel_opts, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
                    GF_CALL_ICMP6_TIME_EXCEEDED, GF_REC_EGRESS, GF_REC_PIPELINE)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
@@ -294,9 +294,12 @@ class Datapath:
                                                _stream()), "gf_pipeline_classify_tunnel")
         return out, nd6, snap, tun
 
-    def overlay(self, b, now, out=None, snap_out=True):
+    def overlay(self, b, now, out=None, snap_out=True, opt=None, opt_len=None):
         """from-overlay over the batch's inner frames and tunnel ids (+ handle_policy of
-        the local deliveries): returns (records [n,24] u8, rewritten snaps or None)."""
+        the local deliveries): returns (records [n,24] u8, rewritten snaps or None).
+        opt [n,opt_stride] u8 / opt_len [n] u8 (device tensors): the packets' tunnel options, for
+        a program loaded with GF_OVERLAY_F_GENEVE (gf_overlay_classify_opts); given either of
+        them the call goes there, with neither to gf_overlay_classify."""
         torch = _torch()
         if out is None:
             out = torch.empty((b.n, 24), dtype=torch.uint8, device=b.device)
@@ -304,9 +307,28 @@ class Datapath:
         stride = b.frames.shape[1] if b.n else 64
         ob = gf_overlay_batch(gf_frames(b.n, stride, _ptr(b.frames), _ptr(b.len)), _ptr(b.tunnel_id), _ptr(b.tc_index),
                               _ptr(b.flow_hash))
-        _check(lib.gf_overlay_classify(self.ovl, C.byref(ob), now, _ptr(out), _ptr(snap), _stream()),
-               "gf_overlay_classify")
+        if opt is None and opt_len is None:
+            _check(lib.gf_overlay_classify(self.ovl, C.byref(ob), now, _ptr(out), _ptr(snap), _stream()),
+                   "gf_overlay_classify")
+        else:
+            to = gf_tunnel_opts(_ptr(opt), opt.shape[1] if opt is not None and opt.dim() == 2 else 0, _ptr(opt_len))
+            _check(lib.gf_overlay_classify_opts(self.ovl, C.byref(ob), C.byref(to), now, _ptr(out), _ptr(snap),
+                                                _stream()), "gf_overlay_classify_opts")
         return out, snap
+
+    def egress_tunnel_meta(self, lxc_id, records):
+        """gf_lxc_egress_tunnel_meta: what encap_and_redirect sets besides the record's tunnel_ip for
+        the GF_EG_F_ENCAP records of egress() — lxc_id [n] i16 the batch's column, records [n,24] u8.
+        Returns (tunnel_id [n] i32, opt [n,8] u8, opt_len [n] u8): the sender's SECLABEL, its
+        GENEVE_OPTS and 8; zeros for every other record.  The layout overlay() takes."""
+        torch = _torch()
+        n = records.shape[0]
+        tid = torch.empty(n, dtype=torch.int32, device=records.device)
+        opt = torch.empty((n, 8), dtype=torch.uint8, device=records.device)
+        ol = torch.empty(n, dtype=torch.uint8, device=records.device)
+        _check(lib.gf_lxc_egress_tunnel_meta(self.policy_array, _ptr(lxc_id), _ptr(records), n, _ptr(tid), _ptr(opt),
+                                             _ptr(ol), _stream()), "gf_lxc_egress_tunnel_meta")
+        return tid, opt, ol
 
     def from_host(self, b, now, out=None, snap_out=True):
         """from-host (cilium_host) over the batch's frames and marks (+ handle_policy of the
