@@ -239,6 +239,7 @@ struct PolicyArray : Obj {
     bool dirty = true;
     uint64_t gen = 0;          // bumped by every gf_policy_array_update (ProgRespond's table follows it)
     int noct = 0;              // programs with GF_LXC_F_NO_CONNTRACK: 0 none, 1 some, 2 every one (gf_policy_array_update)
+    bool dbg = false;          // a program with GF_LXC_F_DEBUG is bound (gf_policy_array_update)
     std::mutex mu;             // one classify call at a time per array (its device image)
     OrderPt ord;
     PolicyArray() : Obj(ObjKind::PolicyArray) {}

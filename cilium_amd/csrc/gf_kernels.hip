@@ -1106,10 +1106,11 @@ __device__ __forceinline__ void ct_hit(const gf_htab_desc &d, int64_t f, uint4 h
 // probe of tf, answered by one walk.  On return t holds the tuple the reference
 // leaves in *tuple (tf unless the first probe hit), *tfl its flags, and pr the
 // walk (its EMPTY slot is where ct_create inserts).
-template <int KSZ, int TW, int U>
+// DBG: *life receives the matched entry's lifetime as stored (DBG_CT_MATCH, conntrack.h:84)
+template <int KSZ, int TW, int U, bool DBG = false>
 __device__ __forceinline__ int ct_lookup(const gf_htab_desc &d, ProbeLine<KSZ, U, 4> &L, uint32_t *t, uint32_t nh,
                                          uint32_t &tfl, int action, bool syn, uint32_t len, uint32_t now, bool acct,
-                                         CtState &st, ProbeRes &pr, uint32_t &ab) {
+                                         CtState &st, ProbeRes &pr, uint32_t &ab, uint32_t *life = nullptr) {
     constexpr int AW = (TW - 2) / 2;                   // address words per side
     uint32_t tf[TW];
 #pragma unroll
@@ -1129,6 +1130,7 @@ __device__ __forceinline__ int ct_lookup(const gf_htab_desc &d, ProbeLine<KSZ, U
             hot = gload<uint4>(ht_val(d, (uint64_t)pr.f));
         }
     }
+    if constexpr (DBG) *life = hot.x;
     if (pr.f >= 0 && !pr.is_b) {
         ct_hit(d, pr.f, hot, action, syn, len, now, acct, st, ab);
         return (tfl & 2u) ? CT_RELATED : CT_REPLY;
@@ -1448,12 +1450,58 @@ deny:
     return D_POLICY;
 }
 
+// Debug notifications (bpf/lib/dbg.h, DEBUG; GF_LXC_F_DEBUG).  Like the traces,
+// the records are written by the event pass; the debug instantiation of
+// k_ing_groups leaves, per packet of a program with the flag, what neither the
+// verdict record nor gf_rec nor the program can tell: one 32-B entry.
+//   w0  GF_DBG_* bits: the messages handle_policy sent | l4_proxy_lookup's result << 16
+//   w1  DBG_CT_MATCH: entry->lifetime as stored when the lookup found it
+//   w2  the matched entry's rev_nat_index (== ct_state.rev_nat_index at DBG_CT_VERDICT)
+//   w3  ct_lookup's return value
+//   w4  the dport the policy was asked with (tuple.dport after the lookup, raw be16)
+//   w5  the redirect's new_port (raw be16; the record loses it on DROP_PROXYMAP_CREATE_FAILED)
+//   w6, w7  IPv6: tuple.saddr.p4, tuple.daddr.p4 (DBG_CT_LOOKUP6_1; daddr.p4 & 0xffff is
+//       DBG_CT_CREATED6's rev_nat_index)
+// An entry of all zeros expands to nothing (the column is cleared before the launch).
+#define GF_DBG_LOOKUP   (1u << 0)   // ct_lookup reached its first message: LOOKUP*_1, LOOKUP*_2, CT_VERDICT
+#define GF_DBG_SKIP     (1u << 1)   // DBG_SKIP_PROXY
+#define GF_DBG_MATCH    (1u << 2)   // DBG_CT_MATCH
+#define GF_DBG_L4_KEY   (1u << 3)   // DBG_L4_CREATE: the {identity, dport, proto} key hit
+#define GF_DBG_L4_PROXY (1u << 4)   // l4_proxy_lookup ran: DBG_GENERIC, DBG_L4_POLICY
+#define GF_DBG_DENIED   (1u << 5)   // DBG_POLICY_DENIED
+#define GF_DBG_CREATED  (1u << 6)   // DBG_CT_CREATED4/6 (sent before the map update)
+#define GF_DBG_CAPTURE  (1u << 7)   // the redirect got to DBG_CAPTURE_PROXY_POST (IPv4: + DBG_REV_PROXY_UPDATE)
+struct DbgLog {
+    uint32_t w[8];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int k = 0; k < 8; k++) w[k] = 0;
+    }
+};
+// The memo keeps which key answered in two spare bits of PolDecision::slab (the
+// algorithmic bytes of a decision stay far below 2^14): debug instantiation only.
+#define GF_MEMO_DBG_L4_KEY   (1u << 30)
+#define GF_MEMO_DBG_L4_PROXY (1u << 31)
+// Which key of __policy_can_access answered (policy.h:60-108), from the entry it
+// counted: slot fc of the program's policy map (key words 0-1, proxy_port at byte 10).
+__device__ __attribute__((noinline)) uint32_t pol_dbg_key_ol(const uint8_t *slot, uint32_t identity, uint32_t pk,
+                                                             uint32_t proto) {
+    const uint4 e = gload<uint4>(slot);
+    if (e.y == 0u) return 0u;                           // the L3 key {identity, 0, 0}: no message
+    uint32_t b = 0;
+    if (e.x == identity && e.y == pk) b |= GF_MEMO_DBG_L4_KEY;     // the first lookup (also when identity is 0)
+    if (!(e.z >> 16) && (proto == 6 || proto == 17)) b |= GF_MEMO_DBG_L4_PROXY;   // proxy_port 0: l4_proxy_lookup
+    return b;
+}
+
 // policy_can_access_ingress with the counter update (policy.h:67-92), through the
 // lane's decision memo (IPv4, or any non-reserved identity).
-template <int N>
+// DBG: *dk receives the GF_DBG_L4_KEY / L4_PROXY / DENIED bits of the decision.
+template <int N, bool DBG = false>
 __device__ __forceinline__ int policy_ingress(const IngCtx &X, Ep &ep, PolLine &pl, bool pl_loaded, uint32_t identity,
                                               uint32_t dport, uint32_t proto, uint32_t len, bool v6,
-                                              const uint32_t *cidr_addr, uint32_t &ab, PolAcc &acc, PolMemo<N> &m) {
+                                              const uint32_t *cidr_addr, uint32_t &ab, PolAcc &acc, PolMemo<N> &m,
+                                              uint32_t *dk = nullptr) {
     const uint32_t pk = dport | (proto << 16), sip = v6 ? 0u : cidr_addr[0];
 #if GF_DIAG & 16
     // diagnosis (ceiling of any policy-map staging): no policy-map read, the counter
@@ -1465,7 +1513,13 @@ __device__ __forceinline__ int policy_ingress(const IngCtx &X, Ep &ep, PolLine &
     const int j = memo_ok ? m.find(ep.sl, identity, pk, sip) : -1;
     if (j >= 0) {
         const PolDecision &d = m.d[j];
-        ab += d.slab >> 16;
+        if constexpr (DBG) {
+            ab += (d.slab >> 16) & 0x3fffu;
+            *dk = ((d.slab & GF_MEMO_DBG_L4_KEY) ? GF_DBG_L4_KEY : 0u) | ((d.slab & GF_MEMO_DBG_L4_PROXY) ? GF_DBG_L4_PROXY : 0u) |
+                  (d.verdict < 0 ? GF_DBG_DENIED : 0u);
+        } else {
+            ab += d.slab >> 16;
+        }
         if (d.f != ~0u) policy_count(X, ep, (int64_t)d.f, len, acc);
         return d.verdict;
     }
@@ -1473,11 +1527,19 @@ __device__ __forceinline__ int policy_ingress(const IngCtx &X, Ep &ep, PolLine &
     int64_t fc;
     int v = policy_lookup(X, ep, pl, pl_loaded, identity, dport, proto, v6, cidr_addr, ab, fc);
     if (fc >= 0) policy_count(X, ep, fc, len, acc);
+    uint32_t mk = 0;
+    if constexpr (DBG) {
+        // (no message without POLICY_INGRESS: policy_can_access_ingress is the stub, policy.h:170-178)
+        if (fc >= 0 && (ep.flags & GF_LXC_F_HAVE_L4_POLICY))
+            mk = pol_dbg_key_ol(ep.pol + (uint64_t)fc * GF_POL_SLOT, identity, pk, proto);
+        *dk = ((mk & GF_MEMO_DBG_L4_KEY) ? GF_DBG_L4_KEY : 0u) | ((mk & GF_MEMO_DBG_L4_PROXY) ? GF_DBG_L4_PROXY : 0u) |
+              (v < 0 ? GF_DBG_DENIED : 0u);
+    }
     if (memo_ok) {
         PolDecision &d = m.victim(ep.next);
         d.id = identity; d.pk = pk; d.sip = sip; d.verdict = v;
         d.f = fc >= 0 ? (uint32_t)fc : ~0u;    // policy maps hold < 2^32 slots (max_entries is u32)
-        d.slab = ep.sl | ((ab - ab0) << 16);
+        d.slab = ep.sl | ((ab - ab0) << 16) | mk;
     }
     return v;
 }
@@ -1570,13 +1632,15 @@ __device__ __attribute__((noinline)) void pol_redirect_ol(PolCtx X, uint32_t i, 
 // rlog: X.rlog unless the run fell back to pair groups (read once per kernel, k_ing_groups);
 // RL: the instance has the egress connection groups' related-entry path at all (the
 // egress deliveries' pass), kept out of the others' registers
-template <bool PCT, bool RL = false>
+// DBG: the debug instantiation fills *dl (DbgLog) as the messages are sent
+template <bool PCT, bool RL = false, bool DBG = false>
 __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i, int &fwd, uint8_t &ofl, uint16_t &proxy,
                            uint32_t &ifindex, int *added, uint32_t &ab, PolAcc &acc, RelCache<4> &rc, PolMemo<GF_MEMO4> &pm,
-                           uint32_t *rlog) {
+                           uint32_t *rlog, DbgLog *dl = nullptr) {
     uint32_t len = r.len;
     if (len < 34) return D_INVALID;
     const uint32_t flags = ep.flags;
+    if constexpr (DBG) if (r.cls & 4) dl->w[0] |= GF_DBG_SKIP;   // tc_index_skip_proxy (lxc.h:196-205)
     uint32_t nh = r.proto;
     uint32_t t[4] = {r.daddr, r.saddr, 0u, nh};
     uint32_t tfl = 0;                                   // TUPLE_F_OUT (ingress)
@@ -1605,7 +1669,14 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
     bool acct = (flags & GF_LXC_F_CT_ACCOUNTING) != 0;
     CtState st{0, 0, 0};
     ProbeRes pr;
-    int ret = ct_lookup<14, 4, GF_CT4_U>(ct, cl, t, nh, tfl, action, syn, len, X.now, acct, st, pr, ab);
+    int ret;
+    if constexpr (DBG) {
+        ret = ct_lookup<14, 4, GF_CT4_U, true>(ct, cl, t, nh, tfl, action, syn, len, X.now, acct, st, pr, ab, &dl->w[1]);
+        dl->w[0] |= GF_DBG_LOOKUP | (ret != CT_NEW ? GF_DBG_MATCH : 0u);
+        dl->w[2] = st.rev_nat; dl->w[3] = (uint32_t)ret;
+    } else {
+        ret = ct_lookup<14, 4, GF_CT4_U>(ct, cl, t, nh, tfl, action, syn, len, X.now, acct, st, pr, ab);
+    }
     fwd = ret;
     if (st.carry) rel_drop(PCT ? ct : X.ct4, rc, X.now);   // a counter carry touched a cold value part
     if (ret == CT_REPLY && st.rev_nat && !st.loopback) {
@@ -1622,8 +1693,17 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
         }
     }
     uint32_t orig_sip = r.saddr;
-    int verdict = (GF_DIAG & 4) ? 0 : policy_ingress(X, ep, pl, pre, r.src_identity, t[2] & 0xffffu, nh, len, false,
+    int verdict;
+    if constexpr (DBG) {
+        uint32_t dk = 0;
+        verdict = policy_ingress<GF_MEMO4, true>(X, ep, pl, pre, r.src_identity, t[2] & 0xffffu, nh, len, false, &orig_sip, ab,
+                                                 acc, pm, &dk);
+        dl->w[0] |= dk | ((dk & GF_DBG_L4_PROXY) ? (uint32_t)verdict << 16 : 0u);
+        dl->w[4] = t[2] & 0xffffu;
+    } else {
+        verdict = (GF_DIAG & 4) ? 0 : policy_ingress(X, ep, pl, pre, r.src_identity, t[2] & 0xffffu, nh, len, false,
                                                      &orig_sip, ab, acc, pm);
+    }
     if (ret != CT_REPLY && ret != CT_RELATED && verdict < 0) {
         if (ret == CT_ESTABLISHED) {
             ab += 14;
@@ -1634,6 +1714,7 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
     }
     if (r.cls & 4) verdict = 0;                         // skip_proxy
     if (ret == CT_NEW && !(GF_DIAG & 8)) {
+        if constexpr (DBG) dl->w[0] |= GF_DBG_CREATED;
         ret = ct_create<14, 4, GF_CT4_U>(ct, t, 0u, r.src_identity, len, X.now, X.strict & 1, pr, added, rc, ab,
                                          RL ? rlog : nullptr, X.rlog_n, 2u * i + 1u, &X.rs);
         if (ret < 0) return ret;
@@ -1645,6 +1726,7 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
                         trace_cap_len(len, X.snap_stride), i, GF_TR_PX_POLICY);
         int r3 = redirect_checks(len, r.l4_off, nh);
         if (r3 < 0) return r3;
+        if constexpr (DBG) { dl->w[0] |= GF_DBG_CAPTURE; dl->w[5] = (uint32_t)verdict & 0xffffu; }
         if (X.snap || X.plog) { const uint32_t od[1] = {r.daddr}; pol_redirect(X, i, len, r.l4_off, nh, t, false, (uint32_t)verdict & 0xffffu, od, r.src_identity); }
         ifindex = X.host_ifindex;
         ofl |= GF_INGRESS_F_PROXY;
@@ -1654,14 +1736,15 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
 }
 
 // ipv6_policy, bpf/bpf_lxc.c:745-862
-template <bool PCT>
+template <bool PCT, bool DBG = false>
 __device__ int ipv6_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i, int &fwd, uint8_t &ofl,
                            uint16_t &proxy, uint32_t &ifindex, int *added, uint32_t &ab, PolAcc &acc,
-                           RelCache<10> &rc, PolMemo<GF_MEMO6> &pm) {
+                           RelCache<10> &rc, PolMemo<GF_MEMO6> &pm, DbgLog *dl = nullptr) {
     uint32_t len = r.len;
     if (len < 54) return D_INVALID;
     if (!X.daddr6 || !X.saddr6) return D_INVALID;      // batch built without IPv6 columns
     const uint32_t flags = ep.flags;
+    if constexpr (DBG) if (r.cls & 4) dl->w[0] |= GF_DBG_SKIP;   // tc_index_skip_proxy (lxc.h:196-205)
     uint32_t nh = r.proto;
     uint4 d = gload<uint4>(X.daddr6 + (size_t)X.a6_stride * i);
     uint4 s = gload<uint4>(X.saddr6 + (size_t)X.a6_stride * i);
@@ -1692,7 +1775,15 @@ __device__ int ipv6_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
     bool acct = (flags & GF_LXC_F_CT_ACCOUNTING) != 0;
     CtState st{0, 0, 0};
     ProbeRes pr;
-    int ret = ct_lookup<40, 10, GF_CT6_U>(ct, cl, t, nh, tfl, action, syn, len, X.now, acct, st, pr, ab);
+    int ret;
+    if constexpr (DBG) {
+        dl->w[6] = s.w; dl->w[7] = d.w;
+        ret = ct_lookup<40, 10, GF_CT6_U, true>(ct, cl, t, nh, tfl, action, syn, len, X.now, acct, st, pr, ab, &dl->w[1]);
+        dl->w[0] |= GF_DBG_LOOKUP | (ret != CT_NEW ? GF_DBG_MATCH : 0u);
+        dl->w[2] = st.rev_nat; dl->w[3] = (uint32_t)ret;
+    } else {
+        ret = ct_lookup<40, 10, GF_CT6_U>(ct, cl, t, nh, tfl, action, syn, len, X.now, acct, st, pr, ab);
+    }
     fwd = ret;
     if (st.carry) rc.slot = ~0u;
     if (st.rev_nat) {
@@ -1707,7 +1798,16 @@ __device__ int ipv6_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
             if (X.snap) pol_rev_nat_write_ol(pol_ctx(X), i, len, r.l4_off, nh, nat);
         }
     }
-    int verdict = policy_ingress(X, ep, pl, pre, r.src_identity, t[8] & 0xffffu, nh, len, true, t + 4, ab, acc, pm);
+    int verdict;
+    if constexpr (DBG) {
+        uint32_t dk = 0;
+        verdict = policy_ingress<GF_MEMO6, true>(X, ep, pl, pre, r.src_identity, t[8] & 0xffffu, nh, len, true, t + 4, ab, acc,
+                                                 pm, &dk);
+        dl->w[0] |= dk | ((dk & GF_DBG_L4_PROXY) ? (uint32_t)verdict << 16 : 0u);
+        dl->w[4] = t[8] & 0xffffu;
+    } else {
+        verdict = policy_ingress(X, ep, pl, pre, r.src_identity, t[8] & 0xffffu, nh, len, true, t + 4, ab, acc, pm);
+    }
     if (ret != CT_REPLY && ret != CT_RELATED && verdict < 0) {
         if (ret == CT_ESTABLISHED) {
             ab += 40;
@@ -1718,6 +1818,7 @@ __device__ int ipv6_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
     }
     if (r.cls & 4) verdict = 0;
     if (ret == CT_NEW) {
+        if constexpr (DBG) dl->w[0] |= GF_DBG_CREATED;
         ret = ct_create<40, 10, GF_CT6_U>(ct, t, rn_new, r.src_identity, len, X.now, (X.strict & 2) != 0, pr, added, rc, ab);
         if (ret < 0) return ret;
         ofl |= GF_INGRESS_F_CREATED;
@@ -1728,6 +1829,7 @@ __device__ int ipv6_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
                         trace_cap_len(len, X.snap_stride), i, GF_TR_PX_POLICY);
         int r3 = redirect_checks(len, r.l4_off, nh);
         if (r3 < 0) return r3;
+        if constexpr (DBG) { dl->w[0] |= GF_DBG_CAPTURE; dl->w[5] = (uint32_t)verdict & 0xffffu; }
         if (X.snap || X.plog) {
             V6Tuple tv;
 #pragma unroll
@@ -1803,9 +1905,9 @@ __device__ __forceinline__ void lane_rel_drop(const IngCtx &X, Lane<FAM> &ln) {
 // 4 = the IPv4 path plus every packet that cannot reach conntrack (no IP
 // header: their early returns need no CT code), 6 = IPv6 packets that reach
 // conntrack.  The sort key keeps the two sets in different buckets.
-template <int FAM, bool PCT, bool RL>
+template <int FAM, bool PCT, bool RL, bool DBG = false>
 __device__ __forceinline__ gf_ingress_out handle_policy(const IngCtx &X, const gf_rec &r, uint32_t i, Lane<FAM> &ln,
-                                                       uint32_t &ab, uint32_t *rlog) {
+                                                       uint32_t &ab, uint32_t *rlog, DbgLog *dl = nullptr) {
     gf_ingress_out o{};
     uint32_t sl = r.ep;
     if (!sl) { o.action = TC_SHOT; o.reason = 140; return o; }   // missed tail call (DROP_MISSED_TAIL_CALL)
@@ -1819,13 +1921,13 @@ __device__ __forceinline__ gf_ingress_out handle_policy(const IngCtx &X, const g
     if (flags & GF_LXC_F_DROP_ALL) ret = D_POLICY;
     else if (cls == 2) {
         ab += 47;
-        if constexpr (FAM == 6) ret = ipv6_policy<PCT>(X, ln.ep, r, i, fwd, fl, proxy, ifindex, &ln.added, ab, ln.acc, ln.rc, ln.pm);
+        if constexpr (FAM == 6) ret = ipv6_policy<PCT, DBG>(X, ln.ep, r, i, fwd, fl, proxy, ifindex, &ln.added, ab, ln.acc, ln.rc, ln.pm, dl);
         else ret = D_INVALID;                       // ipv6_policy: short frame or batch without v6 columns
     }
     else if (cls == 1 && (flags & GF_LXC_F_LXC_IPV4)) {
         ab += 23;
-        if constexpr (FAM == 4) ret = ipv4_policy<PCT, RL>(X, ln.ep, r, i, fwd, fl, proxy, ifindex, &ln.added, ab, ln.acc, ln.rc, ln.pm,
-                                                  rlog);
+        if constexpr (FAM == 4) ret = ipv4_policy<PCT, RL, DBG>(X, ln.ep, r, i, fwd, fl, proxy, ifindex, &ln.added, ab, ln.acc, ln.rc, ln.pm,
+                                                  rlog, dl);
         else ret = D_INVALID;                       // (not reached: v4 packets sort into FAM 4 buckets)
     }
     else ret = D_UNKNOWN_L3;
@@ -1901,9 +2003,15 @@ __global__ __launch_bounds__(BLOCK) void k_ing_pack(gf_pkt_cols c, const uint16_
 // (LPT): k_bucket_order lists them by packet count, descending, and waves take
 // the next 64 entries of that list from a device queue, so the lanes of a wave
 // carry equal work and the deepest buckets start first.
-template <int FAM, bool PCT, bool RL>
+// The debug log entry of packet i: two 16-B stores, kept out of line (the IPv6
+// kernel has no registers to spare for the inlined copy).
+__device__ __attribute__((noinline)) void dbg_log_write_ol(uint4 *dlog, uint32_t i, DbgLog dl) {
+    dlog[2 * (size_t)i] = make_uint4(dl.w[0], dl.w[1], dl.w[2], dl.w[3]);
+    dlog[2 * (size_t)i + 1] = make_uint4(dl.w[4], dl.w[5], dl.w[6], dl.w[7]);
+}
+template <int FAM, bool PCT, bool RL, bool DBG = false>
 __device__ __forceinline__ void ing_one(const IngCtx &X, uint32_t i, const gf_rec &r, gf_ingress_out *out,
-                                        Stats &st, bool stats, Lane<FAM> &ln, uint32_t *rlog) {
+                                        Stats &st, bool stats, Lane<FAM> &ln, uint32_t *rlog, uint4 *dlog = nullptr) {
     if (r.cls & 8) return;                              // pipeline: ended before the tail call
     uint32_t ab = 8;                                    // output record
     if constexpr (PCT) {
@@ -1911,7 +2019,17 @@ __device__ __forceinline__ void ing_one(const IngCtx &X, uint32_t i, const gf_re
         // program's map; a packet of another program writes the pending entry first
         if (r.ep != ln.ep.sl) { lane_rel_drop<FAM, true>(X, ln); lane_flush_added<FAM, true>(X, ln); }
     }
-    gf_ingress_out o = handle_policy<FAM, PCT, RL>(X, r, i, ln, ab, rlog);
+    gf_ingress_out o;
+    if constexpr (DBG) {
+        // handle_policy with DEBUG: the log is written per packet, in bucket order, and only
+        // for packets of a program with the flag (the others' entries stay cleared)
+        DbgLog dl;
+        dl.init();
+        o = handle_policy<FAM, PCT, RL, true>(X, r, i, ln, ab, rlog, &dl);
+        if (r.ep && (ln.ep.flags & GF_LXC_F_DEBUG)) dbg_log_write_ol(dlog, i, dl);
+    } else {
+        o = handle_policy<FAM, PCT, RL>(X, r, i, ln, ab, rlog);
+    }
     if (X.pout && X.pout_wo) {                          // complete the pipeline record: stores only
         uint8_t *q = X.pout + 24 * (size_t)i;
         const uint32_t ff = ((uint32_t)(r.cls >> 4) & 7u) << 5;   // the front's whole GF_PIPE_F_* byte
@@ -2085,6 +2203,55 @@ __global__ __launch_bounds__(BLOCK, FAM == 6 ? GF_ING_MINW6 : GF_ING_MINW) void 
     ln.acc.flush(X);
     lane_rel_drop<FAM, PCT>(X, ln);                     // the pending related-entry write (IPv4)
     lane_flush_added<FAM, PCT>(X, ln);                  // (per-endpoint maps: the lane's own count add)
+    if (stats) ln.sc.fold(st);
+    flush_added(X, F ? 2u : 1u, ln.added, ct_count, &sadd);
+    if (stats) st.flush(stats);
+}
+
+// The debug kernel (GF_LXC_F_DEBUG): k_ing_groups' schedule walk (one bucket per lane, GRAB 1, no
+// related-entry log) over the debug instantiation of handle_policy, which also fills the
+// per-packet log (dlog: a 32-B DbgLog per packet).  Launched by
+// gf_policy_ingress_classify(_batches) only, when a ring is set and the array holds a program
+// with the flag.  A copy of the loop, not a shared body: k_ing_groups keeps the code it had.
+template <int FAM, bool PCT>
+__global__ __launch_bounds__(BLOCK, FAM == 6 ? GF_ING_MINW6 : GF_ING_MINW) void k_ing_groups_dbg(IngCtx X, uint32_t *sched,
+                                                      const uint2 *order, const uint32_t *perm,
+                                                      const gf_rec *rec, gf_ingress_out *out, uint32_t *ct_count,
+                                                      unsigned long long *stats, uint4 *dlog) {
+    constexpr int F = FAM == 6 ? 1 : 0;
+    if (GF_SCHED_NFAM(sched)[F] == 0) return;
+    __shared__ uint32_t sl[272];
+    __shared__ uint32_t sadd;
+    Stats st{sl};
+    if (threadIdx.x == 0) sadd = 0;
+    if (stats) st.init(); else __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    __shared__ Lane<FAM> lanes[BLOCK];
+    Lane<FAM> &ln = lanes[threadIdx.x];
+    ln.init();
+    for (uint32_t xi = 0; xi < GF_NCLS; xi++) {
+        const uint32_t L = F * GF_NCLS + (blockIdx.x % GF_NCLS + xi) % GF_NCLS;
+        uint32_t *queue = GF_SCHED_QUEUE(sched) + L;
+        const uint32_t nb = GF_SCHED_LCNT(sched)[L];
+        const uint2 *lorder = order + GF_SCHED_LSTART(sched)[L];
+        for (;;) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(queue, 64u);
+            base = __shfl(base, 0);
+            if (base >= nb) break;
+            const uint32_t t = base + lane;
+            if (t >= nb) continue;
+            const uint2 oc = lorder[t];
+            lane_rel_drop<FAM, PCT>(X, ln);              // a new bucket: new flow groups
+            for (uint32_t k = 0; k < oc.y; k++) {        // the bucket's packets in batch order
+                const uint32_t i = perm[oc.x + k];
+                ing_one<FAM, PCT, false, true>(X, i, ld_rec(rec, i), out, st, stats != nullptr, ln, nullptr, dlog);
+            }
+        }
+    }
+    ln.acc.flush(X);
+    lane_rel_drop<FAM, PCT>(X, ln);
+    lane_flush_added<FAM, PCT>(X, ln);
     if (stats) ln.sc.fold(st);
     flush_added(X, F ? 2u : 1u, ln.added, ct_count, &sadd);
     if (stats) st.flush(stats);
@@ -4223,6 +4390,10 @@ struct EvSrc {
     // from-host (nd_trace's observation point is TR_FROM_HOST): the per-packet choice of
     // TRACE_FROM_HOST / FROM_PROXY is made from the batch's mark column (null: all 0)
     const uint32_t *hmark;
+    // debug notifications (dbg.h; ev_list_dbg): the per-packet DbgLog entries of k_ing_groups_dbg
+    // (null: none) and the batch's tc_index column (DBG_SKIP_PROXY's argument; may be null)
+    const uint4 *dlog;
+    const uint8_t *tc_index;
 };
 // One notification: the 8 header words of struct drop_notify / trace_notify and
 // where its captured bytes come from.
@@ -4348,21 +4519,152 @@ __device__ uint32_t ev_list(const EvSrc &E, uint32_t i, int k, EvOne &out) {
     if (act == TC_SHOT && stage != GF_STAGE_XDP) n++;
     return n;
 }
-__global__ __launch_bounds__(BLOCK) void k_ev_count(EvSrc E, uint32_t *blk) {
+// Debug notifications (bpf/lib/dbg.h:144-214): struct debug_msg (20 B: type
+// CILIUM_NOTIFY_DBG_MSG = 2, subtype, source, hash, arg1..3) and struct
+// debug_capture_msg (24 B: type CILIUM_NOTIFY_DBG_CAPTURE = 3, ..., len_orig, len_cap,
+// arg1, arg2, then len_cap frame bytes).  In EvOne: the header words first, zeros after.
+enum { DBG_GENERIC = 1, DBG_POLICY_DENIED = 5, DBG_CT_MATCH = 8, DBG_CT_VERDICT = 15, DBG_TO_HOST = 19,
+       DBG_REV_PROXY_UPDATE = 40, DBG_L4_POLICY = 41, DBG_CT_LOOKUP4_1 = 44, DBG_CT_LOOKUP4_2 = 45, DBG_CT_CREATED4 = 46,
+       DBG_CT_LOOKUP6_1 = 47, DBG_CT_LOOKUP6_2 = 48, DBG_CT_CREATED6 = 49, DBG_SKIP_PROXY = 50, DBG_L4_CREATE = 51,
+       DBG_CAPTURE_PROXY_POST = 9 };
+__device__ __forceinline__ EvOne ev_dbg(uint32_t sub, uint32_t source, uint32_t hash, uint32_t a1, uint32_t a2,
+                                        uint32_t a3 = 0) {
+    EvOne e;
+    e.w[0] = 2u /* CILIUM_NOTIFY_DBG_MSG */ | (sub << 8) | ((source & 0xffffu) << 16);
+    e.w[1] = hash; e.w[2] = a1; e.w[3] = a2; e.w[4] = a3; e.w[5] = e.w[6] = e.w[7] = 0;
+    e.pay = nullptr; e.pstride = 0;
+    return e;
+}
+__device__ __forceinline__ EvOne ev_dbg_capture(uint32_t sub, uint32_t source, uint32_t hash, uint32_t len, uint32_t a1,
+                                                const uint8_t *pay, uint32_t pstride) {
+    EvOne e;
+    e.w[0] = 3u /* CILIUM_NOTIFY_DBG_CAPTURE */ | (sub << 8) | ((source & 0xffffu) << 16);
+    e.w[1] = hash; e.w[2] = len; e.w[3] = len < GF_TRACE_PAYLOAD_LEN ? len : GF_TRACE_PAYLOAD_LEN;
+    e.w[4] = a1; e.w[5] = e.w[6] = e.w[7] = 0;
+    e.pay = pay; e.pstride = pstride;
+    return e;
+}
+__device__ __forceinline__ uint32_t ev_ntohs(uint32_t v) { return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu); }
+// ev_list for a plain ingress call (kind 0: handle_policy alone) whose array holds a
+// program with GF_LXC_F_DEBUG: the cilium_dbg* messages of handle_policy
+// (bpf_lxc.c:745-1024 and what it calls) expanded from the packet's DbgLog entry in the
+// order they are sent, the program's trace records at their places (TRACE_TO_PROXY
+// inside the redirect, lxc.h:116/168; TRACE_TO_LXC last), then the drop record.
+// It restates ev_list's kind-0 trace and drop records instead of extending ev_list, and
+// ev_write_body keeps ev_list's slot writer next to ev_store, so that k_ev_count /
+// k_ev_write stay the code they were: a change of the drop or trace record layout has
+// to be made in both places.
+__device__ uint32_t ev_list_dbg(const EvSrc &E, uint32_t i, int k, EvOne &out) {
+    const uint8_t *r = E.recs + (size_t)i * E.stride;
+    const uint32_t act = r[E.act_off], reason = r[E.act_off + 1], ct_ret = r[E.act_off + 2], ofl = r[E.act_off + 3];
+    const uint32_t len = E.len[i], hash = E.flow_hash ? E.flow_hash[i] : 0u;
+    const uint8_t *fin = E.snap ? E.snap + (size_t)i * E.snap_stride : nullptr;
+    const uint32_t mark = E.tmark ? E.tmark[i] : 0u;
+    const uint8_t *pxc = (mark & GF_TR_CAPTURED) ? E.tcap_px + (size_t)i * GF_TRACE_PAYLOAD_LEN : fin;
+    const uint32_t pxs = (mark & GF_TR_CAPTURED) ? GF_TRACE_PAYLOAD_LEN : E.snap_stride;
+    const gf_rec pr = E.prec[i];
+    const gf_lxc_dev *dc = pr.ep ? E.cfgs + (pr.ep - 1) : nullptr;
+    const uint32_t pfl = dc ? gload<uint32_t>(&dc->flags) : 0u;
+    const uint32_t lid = dc ? gload<uint32_t>(&dc->lxc_id) : 0u, sec = dc ? gload<uint32_t>(&dc->seclabel) : 0u;
+    const bool tr = E.trace && (pfl & GF_LXC_F_TRACE_NOTIFY);
+    uint32_t lw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (E.dlog && (pfl & GF_LXC_F_DEBUG)) {
+        const uint4 a = E.dlog[2 * (size_t)i], b = E.dlog[2 * (size_t)i + 1];
+        lw[0] = a.x; lw[1] = a.y; lw[2] = a.z; lw[3] = a.w; lw[4] = b.x; lw[5] = b.y; lw[6] = b.z; lw[7] = b.w;
+    }
+    const uint32_t bits = lw[0];
+    const bool v6 = (pr.cls & 3u) == 2u;
+    uint32_t n = 0;
+    auto put = [&](const EvOne &e) { if ((int)n == k) out = e; n++; };
+    if (bits & GF_DBG_SKIP) put(ev_dbg(DBG_SKIP_PROXY, lid, hash, E.tc_index ? E.tc_index[i] : 1u, 0));
+    if (bits & GF_DBG_LOOKUP) {
+        // the tuple before the first __ct_lookup (conntrack.h:265-267, 413-415): ct_l4's port word
+        uint32_t pw = 0, tfl = 0;
+        int action; bool syn;
+        (void)ct_l4(pr.proto, v6, pr, pw, tfl, action, syn);
+        const uint32_t ports = (ev_ntohs(pw >> 16) << 16) | ev_ntohs(pw & 0xffffu);
+        if (v6) put(ev_dbg(DBG_CT_LOOKUP6_1, lid, hash, lw[6], lw[7], ports));
+        else put(ev_dbg(DBG_CT_LOOKUP4_1, lid, hash, pr.saddr, pr.daddr, ports));
+        put(ev_dbg(v6 ? DBG_CT_LOOKUP6_2 : DBG_CT_LOOKUP4_2, lid, hash, ((uint32_t)pr.proto << 8) | tfl, 0));
+        if (bits & GF_DBG_MATCH) put(ev_dbg(DBG_CT_MATCH, lid, hash, lw[1], lw[2]));
+        put(ev_dbg(DBG_CT_VERDICT, lid, hash, lw[3], lw[2]));
+    }
+    if (bits & GF_DBG_L4_KEY) put(ev_dbg(DBG_L4_CREATE, lid, hash, pr.src_identity, sec, (lw[4] << 16) | pr.proto));
+    if (bits & GF_DBG_L4_PROXY) {                       // l4_proxy_lookup (l4.h:191-216)
+        put(ev_dbg(DBG_GENERIC, lid, hash, lw[4], pr.proto));
+        put(ev_dbg(DBG_L4_POLICY, lid, hash, bits >> 16, 1u /* CT_INGRESS */));
+    }
+    if (bits & GF_DBG_DENIED) put(ev_dbg(DBG_POLICY_DENIED, lid, hash, pr.src_identity, sec));
+    if (bits & GF_DBG_CREATED) {
+        if (v6) put(ev_dbg(DBG_CT_CREATED6, lid, hash, lw[7] & 0xffffu, pr.src_identity, 0));
+        else put(ev_dbg(DBG_CT_CREATED4, lid, hash, 0, pr.src_identity, 0));
+    }
+    if (tr && (mark & GF_TR_PX_POLICY))
+        put(ev_trace(TR_TO_PROXY, lid, hash, len, sec, 0, 0, E.host_ifindex, ct_ret, pxc, pxs));
+    if (bits & GF_DBG_CAPTURE) {                        // ipv{4,6}_redirect_to_host_port (lxc.h:133-136, 184)
+        put(ev_dbg_capture(DBG_CAPTURE_PROXY_POST, lid, hash, len, lw[5], fin, E.snap_stride));
+        if (!v6) {
+            put(ev_dbg(DBG_REV_PROXY_UPDATE, lid, hash, ((pr.l4w0 & 0xffffu) << 16) | lw[5], pr.saddr, pr.proto));
+            if (act != TC_SHOT) put(ev_dbg(DBG_TO_HOST, lid, hash, 0, 0));   // (not on DROP_PROXYMAP_CREATE_FAILED)
+        }
+    }
+    if (tr && act != TC_SHOT && !((ofl & GF_INGRESS_F_PROXY) && pr.ifindex != E.host_ifindex))
+        put(ev_trace(TR_TO_LXC, lid, hash, len, pr.src_identity, sec, lid, pr.ifindex, ct_ret, fin, E.snap_stride));
+    if (act == TC_SHOT) {
+        if ((int)n == k) {                              // handle_policy: send_drop_notify(src_label, SECLABEL, LXC_ID, ifindex)
+            out.w[0] = 1u /* CILIUM_NOTIFY_DROP */ | (reason << 8) | (dc ? (lid & 0xffffu) << 16 : 0u);
+            out.w[1] = hash;
+            out.w[2] = len; out.w[3] = len < GF_TRACE_PAYLOAD_LEN ? len : GF_TRACE_PAYLOAD_LEN;
+            out.w[4] = dc ? pr.src_identity & 0xffffu : 0u; out.w[5] = dc ? sec & 0xffffu : 0u;
+            out.w[6] = dc ? lid : 0u; out.w[7] = dc ? pr.ifindex : 0u;
+            out.pay = fin; out.pstride = E.snap_stride;
+        }
+        n++;
+    }
+    return n;
+}
+// One record into its ring slot.  Drop / trace records: 8 header words, the payload
+// at byte 32.  DBG: debug_msg has 5 header words and no payload, debug_capture_msg 6
+// and its payload at byte 24; the rest of the slot is zero-filled either way.
+template <bool DBG>
+__device__ __forceinline__ void ev_store(uint32_t *w, const EvOne &e) {
+    uint32_t hw = 8, cap = e.w[3];
+    if constexpr (DBG) {
+        const uint32_t type = e.w[0] & 0xffu;
+        if (type == 2u) { hw = 5; cap = 0; } else if (type == 3u) hw = 6;
+    }
+    for (uint32_t q = 0; q < 8; q++) if (q < hw) w[q] = e.w[q];
+    for (uint32_t q = hw; q < GF_EVENT_RECORD / 4; q++) {
+        uint32_t v = 0;
+        for (uint32_t b = 0; b < 4; b++) {
+            const uint32_t off = 4 * (q - hw) + b;
+            if (e.pay && off < cap && off < e.pstride) v |= (uint32_t)e.pay[off] << (8 * b);
+        }
+        w[q] = v;
+    }
+}
+template <bool DBG>
+__device__ __forceinline__ uint32_t ev_list_of(const EvSrc &E, uint32_t i, int k, EvOne &out) {
+    if constexpr (DBG) return ev_list_dbg(E, i, k, out);
+    else return ev_list(E, i, k, out);
+}
+template <bool DBG>
+__device__ __forceinline__ void ev_count_body(const EvSrc &E, uint32_t *blk) {
     __shared__ uint32_t c;
     if (threadIdx.x == 0) c = 0;
     __syncthreads();
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     EvOne e;
-    if (i < E.n) { const uint32_t m = ev_list(E, i, -1, e); if (m) atomicAdd(&c, m); }
+    if (i < E.n) { const uint32_t m = ev_list_of<DBG>(E, i, -1, e); if (m) atomicAdd(&c, m); }
     __syncthreads();
     if (threadIdx.x == 0) blk[blockIdx.x] = c;
 }
-__global__ __launch_bounds__(BLOCK) void k_ev_write(EvSrc E, const uint32_t *boff, gf_event_ring R) {
+template <bool DBG>
+__device__ __forceinline__ void ev_write_body(const EvSrc &E, const uint32_t *boff, const gf_event_ring &R) {
     __shared__ uint32_t sc[BLOCK];
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     EvOne e;
-    const uint32_t m = i < E.n ? ev_list(E, i, -1, e) : 0u;
+    const uint32_t m = i < E.n ? ev_list_of<DBG>(E, i, -1, e) : 0u;
     sc[threadIdx.x] = m;
     __syncthreads();
     for (uint32_t o = 1; o < BLOCK; o <<= 1) {          // inclusive scan
@@ -4374,19 +4676,32 @@ __global__ __launch_bounds__(BLOCK) void k_ev_write(EvSrc E, const uint32_t *bof
     for (uint32_t k = 0; k < m; k++) {
         const uint64_t pos = (uint64_t)*R.count + boff[blockIdx.x] + sc[threadIdx.x] - m + k;
         if (pos >= R.capacity) return;                  // ring full: the record is lost
-        ev_list(E, i, (int)k, e);
+        ev_list_of<DBG>(E, i, (int)k, e);
         uint32_t *w = reinterpret_cast<uint32_t *>(R.records + pos * GF_EVENT_RECORD);
-        for (int q = 0; q < 8; q++) w[q] = e.w[q];
-        const uint32_t cap = e.w[3];
-        for (uint32_t q = 0; q < GF_TRACE_PAYLOAD_LEN / 4; q++) {
-            uint32_t v = 0;
-            for (uint32_t b = 0; b < 4; b++) {
-                const uint32_t off = 4 * q + b;
-                if (e.pay && off < cap && off < e.pstride) v |= (uint32_t)e.pay[off] << (8 * b);
+        if constexpr (DBG) {
+            ev_store<true>(w, e);
+        } else {
+            for (int q = 0; q < 8; q++) w[q] = e.w[q];
+            const uint32_t cap = e.w[3];
+            for (uint32_t q = 0; q < GF_TRACE_PAYLOAD_LEN / 4; q++) {
+                uint32_t v = 0;
+                for (uint32_t b = 0; b < 4; b++) {
+                    const uint32_t off = 4 * q + b;
+                    if (e.pay && off < cap && off < e.pstride) v |= (uint32_t)e.pay[off] << (8 * b);
+                }
+                w[8 + q] = v;
             }
-            w[8 + q] = v;
         }
     }
+}
+__global__ __launch_bounds__(BLOCK) void k_ev_count(EvSrc E, uint32_t *blk) { ev_count_body<false>(E, blk); }
+__global__ __launch_bounds__(BLOCK) void k_ev_write(EvSrc E, const uint32_t *boff, gf_event_ring R) {
+    ev_write_body<false>(E, boff, R);
+}
+// the same two passes over ev_list_dbg (a call whose array holds a program with GF_LXC_F_DEBUG)
+__global__ __launch_bounds__(BLOCK) void k_ev_count_dbg(EvSrc E, uint32_t *blk) { ev_count_body<true>(E, blk); }
+__global__ __launch_bounds__(BLOCK) void k_ev_write_dbg(EvSrc E, const uint32_t *boff, gf_event_ring R) {
+    ev_write_body<true>(E, boff, R);
 }
 __global__ void k_ev_commit(const uint32_t *boff, const uint32_t *blk, uint32_t nb, gf_event_ring R) {
     *R.count += boff[nb - 1] + blk[nb - 1];
@@ -6326,6 +6641,7 @@ int gf_lxc_prog_load(const gf_lxc_cfg *cfg) {
     // CONNTRACK_ACCOUNTING mean nothing to the stub ct_* (conntrack.h:582-617)
     const bool noct = (cfg->flags & GF_LXC_F_NO_CONNTRACK) != 0;
     if (noct && (cfg->n_l4_ingress || cfg->n_l4_egress)) return -EINVAL;
+    if (noct && (cfg->flags & GF_LXC_F_DEBUG)) return -EOPNOTSUPP;   // (the CT-off kernel sends no debug messages)
     auto p = std::make_shared<ProgLxc>();
     p->cfg = *cfg;
     if (noct) { p->cfg.ct_map4 = p->cfg.ct_map6 = 0; p->cfg.flags &= ~GF_LXC_F_CT_ACCOUNTING; }
@@ -6411,6 +6727,9 @@ int gf_policy_array_update(int array, uint32_t lxc_id, int prog) {
     for (auto &kv : a->slots)
         if (kv.second->cfg.flags & GF_LXC_F_NO_CONNTRACK) off++;
     a->noct = !off ? 0 : off == a->slots.size() ? 2 : 1;
+    a->dbg = false;                                     // any program with DEBUG
+    for (auto &kv : a->slots)
+        if (kv.second->cfg.flags & GF_LXC_F_DEBUG) a->dbg = true;
     return 0;
 }
 
@@ -6445,6 +6764,18 @@ static bool array_traces(const std::shared_ptr<PolicyArray> &a) {
 // Programs without conntrack (GF_LXC_F_NO_CONNTRACK) in an array: 0 none, 1 some, 2 every one.
 // Kept on the array by gf_policy_array_update (a program's flags never change).
 static int array_noct(const std::shared_ptr<PolicyArray> &a) { return a->noct; }
+// Debug notifications of a plain ingress call: the per-packet log column (DbgLog), cleared.
+struct DbgWs { DevBuf log; };
+static DbgWs &dbg_ws() { static const char tag = 0; return cur_ctx().get<DbgWs>(&tag); }
+// (32 B per packet of the batch, kept for the context's later calls: a call that cannot get it
+// fails with -ENOMEM although the same call without a debug program would run; gpuflow.h says so)
+static int dbg_prepare(uint32_t n, hipStream_t s) {
+    DbgWs &d = dbg_ws();
+    const size_t want = (size_t)n * 32;
+    int r;
+    if (d.log.bytes < want && (r = d.log.ensure(want))) return r;
+    return hip_ok(hipMemsetAsync(d.log.p, 0, want, s), "debug log");
+}
 
 static int trace_prepare(uint32_t n, bool with_in, hipStream_t s) {
     TraceWs &t = trace_ws();
@@ -6457,7 +6788,7 @@ static int trace_prepare(uint32_t n, bool with_in, hipStream_t s) {
 }
 
 // Drop (and trace) notifications of one classify call (no-op without an event ring).
-static int emit_drop_events(EvSrc E, hipStream_t s) {
+static int emit_drop_events(EvSrc E, hipStream_t s, bool dbg = false) {
     gf_event_ring R = event_ring();
     if (!R.records || !R.count || !R.capacity || E.n == 0) return 0;
     struct EvWs { DevBuf blk, boff, tmp; };
@@ -6472,12 +6803,14 @@ static int emit_drop_events(EvSrc E, hipStream_t s) {
     (void)rocprim::exclusive_scan(nullptr, tb, (uint32_t *)blk.p, (uint32_t *)boff.p, 0u, nb, rocprim::plus<uint32_t>(), s);
     if ((r = grow(tmp, tb + 256))) return r;
     ProfScope ps("k_drop_events", s);
-    hipLaunchKernelGGL(k_ev_count, dim3(nb), dim3(BLOCK), 0, s, E, (uint32_t *)blk.p);
+    if (dbg) hipLaunchKernelGGL(k_ev_count_dbg, dim3(nb), dim3(BLOCK), 0, s, E, (uint32_t *)blk.p);
+    else hipLaunchKernelGGL(k_ev_count, dim3(nb), dim3(BLOCK), 0, s, E, (uint32_t *)blk.p);
     tb = tmp.bytes;
     if (hip_ok(rocprim::exclusive_scan(tmp.p, tb, (uint32_t *)blk.p, (uint32_t *)boff.p, 0u, nb,
                                        rocprim::plus<uint32_t>(), s), "event scan"))
         return -EIO;
-    hipLaunchKernelGGL(k_ev_write, dim3(nb), dim3(BLOCK), 0, s, E, (const uint32_t *)boff.p, R);
+    if (dbg) hipLaunchKernelGGL(k_ev_write_dbg, dim3(nb), dim3(BLOCK), 0, s, E, (const uint32_t *)boff.p, R);
+    else hipLaunchKernelGGL(k_ev_write, dim3(nb), dim3(BLOCK), 0, s, E, (const uint32_t *)boff.p, R);
     hipLaunchKernelGGL(k_ev_commit, dim3(1), dim3(1), 0, s, (const uint32_t *)boff.p, (const uint32_t *)blk.p, nb, R);
     return hip_ok(hipGetLastError(), "k_drop_events");
 }
@@ -7197,6 +7530,10 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     // egress callers (whose earlier kernels mark packets) pass their decision
     const bool tracing = ta ? ta->on : (event_ring().records && array_traces(a));
     if (tracing && !ta && (r = trace_prepare(pkts->n, false, s))) return r;
+    // debug notifications (GF_LXC_F_DEBUG): the plain ingress call only; every other entry
+    // point (ta non-null) runs such programs as if the flag were clear
+    const bool debugging = !ta && event_ring().records && a->dbg && noct != 2;
+    if (debugging && (r = dbg_prepare(pkts->n, s))) return r;
     // 1. sync tables, build the device program table
     std::vector<std::shared_ptr<ProgLxc>> progs;
     host_mark("ing");
@@ -7262,6 +7599,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     memcpy(X.host6, node.host_ip6, 16);
     if (tracing) { X.tmark = (uint8_t *)trace_ws().mark.p; X.tcap = (uint8_t *)trace_ws().px.p; }
     if (ta) { X.rlog = ta->rlog; X.rlog_n = ta->rlog_n; X.rlog_off = ta->rlog_off; X.rs = ta->rs; }
+    uint4 *dlog = debugging ? (uint4 *)dbg_ws().log.p : nullptr;
     if ((r = px_log_begin(n, s, X, px_keep))) return r;
     // Non-strict mode accounts each kernel's net element change into its family's map.
     uint32_t *cnt4 = ct4m ? (uint32_t *)ct4m->d_count.p : nullptr, *cnt6 = ct6m ? (uint32_t *)ct6m->d_count.p : nullptr;
@@ -7273,7 +7611,15 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
         if (grid > need) grid = need;
         {
             ProfScope ps("k_ing_groups", s);
-            if (cm.pct)                                 // per-endpoint CT maps (ConntrackLocal)
+            if (debugging && cm.pct)                    // a program with DEBUG: the instantiations that log
+                hipLaunchKernelGGL((k_ing_groups_dbg<4, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
+                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
+                                   nullptr, sink, dlog);
+            else if (debugging)
+                hipLaunchKernelGGL((k_ing_groups_dbg<4, false>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
+                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
+                                   cnt4, sink, dlog);
+            else if (cm.pct)                            // per-endpoint CT maps (ConntrackLocal)
                 hipLaunchKernelGGL((k_ing_groups<4, 1, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
                                    (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
                                    nullptr, sink);
@@ -7288,7 +7634,15 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
         }
         if (pkts->saddr6) {    // IPv6 packets reach conntrack only with v6 columns
             ProfScope ps("k_ing_groups6", s);
-            if (cm.pct)
+            if (debugging && cm.pct)
+                hipLaunchKernelGGL((k_ing_groups_dbg<6, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
+                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
+                                   nullptr, sink, dlog);
+            else if (debugging)
+                hipLaunchKernelGGL((k_ing_groups_dbg<6, false>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
+                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
+                                   cnt6, sink, dlog);
+            else if (cm.pct)
                 hipLaunchKernelGGL((k_ing_groups<6, 1, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
                                    (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
                                    nullptr, sink);
@@ -7329,7 +7683,8 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
                 E.slot_of = (const uint16_t *)a->d_slot_of_lxc.p;
             }
         }
-        if ((r = emit_drop_events(E, s))) return r;
+        if (debugging) { E.dlog = (const uint4 *)dbg_ws().log.p; E.tc_index = pkts->tc_index; E.host_ifindex = host_ifindex(); }
+        if ((r = emit_drop_events(E, s, debugging))) return r;
     }
     host_mark("px+ev");
     for (auto &p : progs) {

@@ -1262,6 +1262,7 @@ def ct6_prefill(meta, reply_keys, reply_vals, now, seed=0xC1D40055):
 # ------------------------------------------------------------------ endpoint egress (from-container)
 LXC_POLICY_EGRESS = 32
 LXC_TRACE_NOTIFY = 64          # TRACE_NOTIFY (pkg/endpoint/endpoint.go:131-134)
+LXC_DEBUG = 256                # GF_LXC_F_DEBUG: DEBUG (pkg/endpoint/endpoint.go:84,162)
 NETDEV_TRACE_NOTIFY = 2
 NETDEV_HANDLE_NS = 4           # GF_NETDEV_F_HANDLE_NS
 NETDEV_ENCAP = 8               # GF_NETDEV_F_ENCAP

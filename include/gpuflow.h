@@ -267,6 +267,16 @@ int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out,
                                                array for gf_policy_ingress_classify(_batches) and gf_pipeline_classify.
                                                gf_lxc_egress_classify returns -EOPNOTSUPP for an array that holds one,
                                                before any launch and without touching any state. */
+#define GF_LXC_F_DEBUG           (1u << 8)  /* DEBUG with EVENT_SOURCE = LXC_ID: the endpoint's Debug option
+                                               (pkg/endpoint/endpoint.go:84,162).  handle_policy's cilium_dbg* messages
+                                               go to the event ring, see "debug notifications" below.  Only
+                                               gf_policy_ingress_classify and gf_policy_ingress_classify_batches emit
+                                               them (IPv4 and IPv6); gf_pipeline_classify*, gf_lxc_egress_classify,
+                                               gf_overlay_classify* and gf_host_classify run a program that has the flag
+                                               exactly as if it were clear.  Together with GF_LXC_F_NO_CONNTRACK:
+                                               gf_lxc_prog_load returns -EOPNOTSUPP before anything is bound.  LB_DEBUG
+                                               (the cilium_dbg_lb messages of lb4/6_rev_nat, bpf/lib/lb.h:84-89) is a
+                                               separate option and is not built. */
 #define GF_MAX_L4_INGRESS 64
 #define GF_MAX_PORTMAP 16
 typedef struct gf_portmap {    /* struct portmap (bpf/lib/common.h), LXC_PORT_MAPPINGS entries */
@@ -824,6 +834,33 @@ int gf_ct_evict_log(int map, gf_ct_evict_rec *out, uint32_t max);
  * in the order the programs send them (from_netdev / handle_ingress first, the
  * drop record last), packets in batch order.  Call sites: bpf_lxc.c:364,381,
  * 650,669,705,1014, lib/lxc.h:116,168, lib/encap.h:67, bpf_netdev.c:436. */
+/* ---- debug notifications (bpf/lib/dbg.h:144-214, DEBUG) ----
+ * Programs loaded with GF_LXC_F_DEBUG also append, through
+ * gf_policy_ingress_classify(_batches) only, the cilium_dbg* messages of
+ * handle_policy (bpf_lxc.c:745-1024, lib/conntrack.h, lib/policy.h, lib/l4.h,
+ * lib/lxc.h), one GF_EVENT_RECORD slot each, zero-filled past what the
+ * reference writes:
+ *   struct debug_msg (20 B: type CILIUM_NOTIFY_DBG_MSG=2, subtype = DBG_*,
+ *   source = EVENT_SOURCE = LXC_ID, hash, arg1, arg2, arg3; arg3 = 0 for the
+ *   two-argument cilium_dbg) and
+ *   struct debug_capture_msg (24 B: type CILIUM_NOTIFY_DBG_CAPTURE=3, subtype =
+ *   DBG_CAPTURE_*, source, hash, len_orig, len_cap, arg1, arg2) followed directly
+ *   (offset 24) by len_cap frame bytes: zeros here, column batches carry no frames
+ * (the layouts pkg/monitor/datapath_debug.go DebugMsg / DebugCapture decode).
+ * Per packet, in the order sent: DBG_SKIP_PROXY; DBG_CT_LOOKUP4_1/_2 (6_1/_2);
+ * at most one DBG_CT_MATCH (the entry's lifetime as stored when the lookup found
+ * it, its rev_nat_index); DBG_CT_VERDICT; DBG_L4_CREATE; DBG_GENERIC +
+ * DBG_L4_POLICY (l4_proxy_lookup); DBG_POLICY_DENIED (also for reply / related
+ * packets, which pass anyway); DBG_CT_CREATED4/6 (also before
+ * DROP_CT_CREATE_FAILED); in the redirect TRACE_TO_PROXY (if traced), then
+ * DBG_CAPTURE_PROXY_POST, DBG_REV_PROXY_UPDATE (IPv4), DBG_TO_HOST (IPv4, not on
+ * DROP_PROXYMAP_CREATE_FAILED); then TRACE_TO_LXC or the drop record, last.
+ * DROP_INVALID, DROP_UNKNOWN_L3 and DROP_ALL packets send no message at all;
+ * DROP_CT_INVALID_HDR and DROP_CT_UNKNOWN_PROTO return before ct_lookup's first
+ * message (at most DBG_SKIP_PROXY, which is sent before the lookup).
+ * The ring-full rule is the drop records'.  Such a call needs 32 B of device
+ * workspace per packet of the batch for the log (kept for later calls); if it
+ * cannot be allocated the call returns -ENOMEM. */
 #define GF_TRACE_PAYLOAD_LEN 128u   /* TRACE_PAYLOAD_LEN, bpf/lib/common.h:213-215 */
 #define GF_EVENT_RECORD 160u
 typedef struct gf_event_ring {
