@@ -2584,10 +2584,27 @@ __global__ __launch_bounds__(BLOCK) void k_single_write(uint32_t n, const uint32
 // packet's handle_policy record and flow-group key directly (k_ing_pack fused);
 // the ingress machinery then runs handle_policy on the packets that reached the
 // tail call and completes their pipeline records in place.
-struct NetdevDev {
+// k_nd_front (a netdev stage with HANDLE_NS or ENCAP_IFINDEX), k_ovl_front (from-overlay)
+// and k_host_front (from-host) are the other frame entry points.  All four are front_body
+// around the entry's own programs: the tile, the record hand-off to ingress_run and the
+// counters exist once.
+
+// cilium_lxc as the entry programs look it up
+struct LxcDev {
     gf_htab_desc lxc;
     const uint32_t *lxset;         // cilium_lxc's IPv4 keys: address set + slots (Map::addr_set), or null
     uint32_t lxbits, lxzero;
+};
+// What the ENCAP_IFINDEX branches read (host_encap4 / 6): the node's tunnel map and cluster range
+struct EncapDev {
+    gf_htab_desc tunnel;
+    const uint32_t *tnset;         // the tunnel map's IPv4 keys (Map::addr_set), or null
+    uint32_t tnbits, tnzero;
+    uint32_t encap_ifindex, cluster_range, cluster_mask, ipv4_mask;
+    uint32_t node6[3];             // first 12 bytes of gf_node_cfg.router_ip6 (ipv6_match_prefix_96)
+};
+struct NetdevDev {
+    LxcDev lx;
     uint32_t flags, fixed_secctx;
     uint32_t router6[2];           // first 8 bytes of ROUTER_IP (LE words)
 };
@@ -2597,6 +2614,30 @@ struct PipeDev {
     NetdevDev nd;
     uint32_t has_xdp, has_lb, lb_redirect_ifindex, vec_copy;
     uint8_t *tcap_in;              // TRACE_FROM_STACK captures (128 B per packet; null: the netdev does not trace)
+};
+// The netdev stage's options (k_nd_front only): from_netdev as bpf/init.sh builds it for the
+// native device (:179 -DHANDLE_NS; ENCAP_IFINDEX from node_config.h in tunnel mode, :303-304)
+struct NdxDev {
+    EncapDev enc;
+    uint32_t router6[4];           // ROUTER_IP (gf_netdev_cfg.router_ip6): icmp6_handle's echo test
+    uint32_t *tunnel_ip;           // bpf_tunnel_key.remote_ipv4 per frame (0: no encap), or null
+};
+
+// One lane's packet on its way through a front kernel: its row in LDS, the header as received,
+// what the entry's programs found out, and the record they fill.
+struct FrontLane {
+    uint32_t i, len, et;
+    Row w;
+    PktHdr h;
+    gf_pipeline_out o;
+    uint32_t sec, ifx, lxc;        // the source identity; cb[CB_IFINDEX] and the lxc_id of the tail call
+    uint32_t mapped, ndport;       // map_lxc_in rewrote the dport
+    uint32_t tun_ip, call, rev;    // encap's remote_ipv4; the responder call; reverse_proxy translated
+    uint32_t ab;                   // algorithmic bytes so far
+    uint32_t tci_or;               // ORed into tc_index for handle_policy
+    bool tail;                     // reached tail_call(cilium_policy)
+    bool keep_sec;                 // not tail: sec stays in the skipped record (an encap redirect:
+                                   // TRACE_TO_OVERLAY's label)
 };
 // lb4_xlate / lb6_xlate writes (bpf/lib/lb.h:615-659, 397-423) of a translation
 // lb_v4/lb_v6 accepted (their checks passed, so every helper succeeds).
@@ -2665,58 +2706,191 @@ __device__ int delivery_tail(Row &w, uint32_t len, int l4_off, uint32_t nh, cons
     return ND_TAILCALL;
 }
 
-// from_netdev of bpf/bpf_netdev.c:395-460 -> handle_ipv4 (:326-393) / handle_ipv6
-// (:160-247), without FROM_HOST, ENCAP_IFINDEX or HANDLE_NS.
-__device__ int pipe_netdev(const NetdevDev &N, Row &w, const PktHdr &h, uint32_t et, uint32_t len,
-                           uint32_t &sec, uint32_t &ifx, uint32_t &lxc, uint32_t &mapped, uint32_t &ndport,
-                           uint32_t &ab) {
-    if (et == 0x0800) {
-        if (len < 34) return D_INVALID;                 // revalidate_data
-        sec = (N.flags & GF_NETDEV_F_FIXED_SECCTX) ? N.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
-        uint32_t kw[5] = {w.r32(30), 0, 0, 0, 1u};      // lookup_ip4_endpoint (post-LB daddr)
-        const int64_t f = N.lxset ? aset_slot(N.lxset, N.lxbits, N.lxzero, kw[0]) : ht_find<20>(N.lxc, kw, key_hash<20>(kw));
+// ---- pieces the entry programs share
+// lookup_ip4_endpoint / lookup_ip6_endpoint: the endpoint's cilium_lxc value, or null
+__device__ __forceinline__ const uint8_t *lxc_lookup4(const LxcDev &X, uint32_t da, uint32_t &ab) {
+    uint32_t kw[5] = {da, 0, 0, 0, 1u};
+    const int64_t f = X.lxset ? aset_slot(X.lxset, X.lxbits, X.lxzero, kw[0]) : ht_find<20>(X.lxc, kw, key_hash<20>(kw));
+    ab += 20;
+    if (f < 0) return nullptr;
+    ab += 8;
+    return ht_val(X.lxc, f);
+}
+__device__ __forceinline__ const uint8_t *lxc_lookup6(const LxcDev &X, const Row &w, uint32_t &ab) {
+    uint32_t kw[5] = {w.r32(38), w.r32(42), w.r32(46), w.r32(50), 2u};
+    const int64_t f = ht_find<20>(X.lxc, kw, key_hash<20>(kw));
+    ab += 20 + 8;
+    if (f < 0) return nullptr;
+    ab += 8;
+    return ht_val(X.lxc, f);
+}
+__device__ __forceinline__ bool ep_is_host(const uint8_t *ep) { return gload<uint32_t>(ep + 8) & 1u; }   // ENDPOINT_F_HOST
+
+// ipv4_dec_ttl (bpf/lib/ipv4.h:30-43) / ipv6_dec_hoplimit (bpf/lib/ipv6.h:178-193): 0, or what
+// the program returns instead of going on
+__device__ __forceinline__ int dec_ttl4(FrontLane &L) {
+    const uint32_t ttl = L.w.b(22);
+    if (ttl <= 1) return D_INVALID;
+    l3_csum(L.w, L.len, 24, ttl, ttl - 1, 2);
+    L.w.w8(22, ttl - 1);
+    L.ab += 3;
+    return 0;
+}
+__device__ __forceinline__ int dec_hoplimit6(FrontLane &L) {
+    const uint32_t hl = L.w.b(21);
+    if (hl <= 1) return ND_ICMP6_TE;
+    L.w.w8(21, hl - 1);
+    L.ab += 1;
+    return 0;
+}
+// ipv4_local_delivery / ipv6_local_delivery (bpf/lib/l3.h:106-168)
+__device__ __forceinline__ int local_delivery4(FrontLane &L, const uint8_t *ep) {
+    if (const int e = dec_ttl4(L)) return e;
+    return delivery_tail(L.w, L.len, L.h.l4, L.h.proto, ep, L.ifx, L.lxc, L.mapped, L.ndport, L.ab);
+}
+__device__ __forceinline__ int local_delivery6(FrontLane &L, const uint8_t *ep) {
+    if (const int e = dec_hoplimit6(L)) return e;
+    return delivery_tail(L.w, L.len, L.h.l4, L.h.proto, ep, L.ifx, L.lxc, L.mapped, L.ndport, L.ab);
+}
+
+// derive_sec_ctx (bpf_netdev.c:50-64) of an IPv6 frame; flags: GF_NETDEV_F_*, router6: the first
+// 8 bytes of ROUTER_IP
+__device__ __forceinline__ uint32_t derive_sec_ctx6(const Row &w, uint32_t flags, uint32_t fixed_secctx,
+                                                    const uint32_t *router6) {
+    if (flags & GF_NETDEV_F_FIXED_SECCTX) return fixed_secctx;
+    if (w.r32(22) == router6[0] && w.r32(26) == router6[1])
+        return __builtin_bswap32(w.r32(14) & __builtin_bswap32(0x000FFFFFu));
+    return 2u;                                          // WORLD_ID
+}
+
+// The ENCAP_IFINDEX branch of handle_ipv4 (:378-393) / handle_ipv6 (:225-243) once the
+// endpoint lookup missed: the cluster-range test and encap_and_redirect's tunnel-map lookup
+// (lib/encap.h:30-70).  true: tun_ip = bpf_tunnel_key.remote_ipv4; false: not in the range, or
+// DROP_NO_TUNNEL_ENDPOINT, which both callers turn into TC_ACT_OK.
+enum { HO_ENCAP = 1003 };
+__device__ __forceinline__ bool host_encap4(const EncapDev &H, uint32_t da, uint32_t &tun_ip, uint32_t &ab) {
+    if (H.encap_ifindex && (da & H.cluster_mask) == H.cluster_range) {
+        uint32_t tk[5] = {da & H.ipv4_mask, 0, 0, 0, 1u};
+        const int64_t ft = H.tnset ? aset_slot(H.tnset, H.tnbits, H.tnzero, tk[0]) : ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
         ab += 20;
-        if (f < 0) return TC_OK;
-        const uint8_t *ep = ht_val(N.lxc, f);
-        ab += 8;
-        if (gload<uint32_t>(ep + 8) & 1u) return TC_OK; // ENDPOINT_F_HOST
-        const uint32_t ttl = w.b(22);                   // ipv4_dec_ttl, bpf/lib/ipv4.h:30-43
-        if (ttl <= 1) return D_INVALID;
-        l3_csum(w, len, 24, ttl, ttl - 1, 2);
-        w.w8(22, ttl - 1);
-        ab += 3;
-        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+        if (ft >= 0) {                                  // encap_and_redirect (lib/encap.h:30-70)
+            tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
+            ab += 20;
+            return true;
+        }
     }
-    if (et == 0x86DD) {
-        if (len < 54) return D_INVALID;
-        sec = 2u;                                       // derive_sec_ctx (bpf_netdev.c:50-64)
-        if (N.flags & GF_NETDEV_F_FIXED_SECCTX) sec = N.fixed_secctx;
-        else if (w.r32(22) == N.router6[0] && w.r32(26) == N.router6[1])
-            sec = __builtin_bswap32(w.r32(14) & __builtin_bswap32(0x000FFFFFu));
-        uint32_t kw[5] = {w.r32(38), w.r32(42), w.r32(46), w.r32(50), 2u};
-        const int64_t f = ht_find<20>(N.lxc, kw, key_hash<20>(kw));
-        ab += 20 + 8;
-        if (f < 0) return TC_OK;
-        const uint8_t *ep = ht_val(N.lxc, f);
-        ab += 8;
-        if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;
-        const uint32_t hl = w.b(21);                    // ipv6_dec_hoplimit, bpf/lib/ipv6.h:178-193
-        if (hl <= 1) return ND_ICMP6_TE;
-        w.w8(21, hl - 1);
-        ab += 1;
-        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+    return false;
+}
+__device__ __forceinline__ bool host_encap6(const EncapDev &H, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t &tun_ip,
+                                            uint32_t &ab) {
+    if (H.encap_ifindex && d0 == H.node6[0] && d1 == H.node6[1] && d2 == H.node6[2]) {
+        uint32_t tk[5] = {d0, d1, d2, 0u, 2u};          // daddr/96
+        const int64_t ft = ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
+        ab += 20;
+        if (ft >= 0) {
+            tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
+            ab += 20;
+            return true;
+        }
+    }
+    return false;
+}
+
+// from_netdev of bpf/bpf_netdev.c:395-460 -> handle_ipv4 (:326-393) / handle_ipv6 (:160-247),
+// without FROM_HOST.  OPTS (k_nd_front; X is null without): the HANDLE_NS block, icmp6_handle
+// (:180-186, lib/icmp6.h:380-401), and the ENCAP_IFINDEX branches (:225-243, :378-392), each
+// behind its GF_NETDEV_F_* flag; k_pipe_front's instance is compiled without them.
+enum { ND_RESPOND = 1004 };
+template <bool OPTS>
+__device__ int pipe_netdev(const NetdevDev &N, const NdxDev *X, FrontLane &L) {
+    const Row &w = L.w;
+    if (L.et == 0x0800) {
+        if (L.len < 34) return D_INVALID;               // revalidate_data
+        L.sec = (N.flags & GF_NETDEV_F_FIXED_SECCTX) ? N.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
+        const uint32_t da = w.r32(30);                  // post-LB daddr
+        const uint8_t *ep = lxc_lookup4(N.lx, da, L.ab);
+        if (!ep) {
+            if constexpr (OPTS)
+                if ((N.flags & GF_NETDEV_F_ENCAP) && host_encap4(X->enc, da, L.tun_ip, L.ab)) return HO_ENCAP;
+            return TC_OK;
+        }
+        if (ep_is_host(ep)) return TC_OK;
+        return local_delivery4(L, ep);
+    }
+    if (L.et == 0x86DD) {
+        if (L.len < 54) return D_INVALID;
+        if constexpr (OPTS) {
+            // HANDLE_NS: nexthdr as ipv6_hdrlen left it (h.proto: a rejected chain keeps
+            // ip6->nexthdr, never 58).  icmp6_load_type (icmp6.h:38-41) is load_byte at the fixed
+            // ETH_HLEN + 40, also behind extension headers; a load past the frame ends the program
+            // with 0 = TC_ACT_OK.
+            if ((N.flags & GF_NETDEV_F_HANDLE_NS) && L.h.proto == 58) {
+                if (L.len < 55) return TC_OK;
+                const uint32_t type = w.b(54);
+                L.ab += 1;
+                if (type == 135) { L.call = GF_CALL_ICMP6_NS; return ND_RESPOND; }   // icmp6_handle_ns (:389-390)
+                if (type == 128 && w.r32(38) == X->router6[0] && w.r32(42) == X->router6[1] &&
+                    w.r32(46) == X->router6[2] && w.r32(50) == X->router6[3]) {   // :391-393
+                    L.call = GF_CALL_ICMP6_ECHO_REPLY;
+                    return ND_RESPOND;
+                }
+            }
+        }
+        L.sec = derive_sec_ctx6(w, N.flags, N.fixed_secctx, N.router6);
+        const uint8_t *ep = lxc_lookup6(N.lx, w, L.ab);
+        if (!ep) {
+            if constexpr (OPTS)
+                if ((N.flags & GF_NETDEV_F_ENCAP) && host_encap6(X->enc, w.r32(38), w.r32(42), w.r32(46), L.tun_ip, L.ab))
+                    return HO_ENCAP;
+            return TC_OK;
+        }
+        if (ep_is_host(ep)) return TC_OK;
+        return local_delivery6(L, ep);
     }
     return TC_OK;                                       // unknown traffic to the stack
 }
 
-// One packet per lane; the block's frames are staged in LDS (BLOCK * snap_stride
-// bytes of dynamic shared memory) and copied back out only when the caller
-// asked for the rewritten frames.
-template <int NT>
-__global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
-                                                      PipeDev P, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
-                                                      uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                      uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
+// ---- the front skeleton
+// TRACE_FROM_*'s capture of the lane's row as it stands (128 B per packet); each entry calls it
+// at its program's send_trace_notify.
+__device__ __forceinline__ void front_capture(const FrontLane &L, uint8_t *tcap_in, uint32_t S, uint32_t vec_copy) {
+    if (!tcap_in) return;
+    uint8_t *d = tcap_in + (size_t)L.i * GF_TRACE_PAYLOAD_LEN;
+    const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
+    if (vec_copy) {
+        for (uint32_t k = 0; k < cb; k += 16)
+            *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(L.w.p + k);
+    } else {
+        for (uint32_t k = 0; k < cb; k++) d[k] = L.w.p[k];
+    }
+}
+
+// An entry program's return value in the record, once the entry has turned its own codes into
+// actions: the port map's rewrite, the tail call, ICMPv6 time exceeded, a drop, or the action.
+// SHOT_DROPS: TC_ACT_SHOT itself is a drop too (the netdev stage, whose LB stage returns it).
+template <bool SHOT_DROPS>
+__device__ __forceinline__ void front_result(FrontLane &L, int r, uint32_t stage) {
+    gf_pipeline_out &o = L.o;
+    if (L.mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)L.ndport; }
+    o.stage = (uint8_t)stage;
+    if (r == ND_TAILCALL) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)L.lxc; L.tail = true; }
+    else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
+    else if (r < 0 || (SHOT_DROPS && r == TC_SHOT)) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }   // send_drop_notify_error
+    else o.action = (uint8_t)r;
+}
+
+// One packet per lane.  The block's frames are staged in LDS (NT * snap_stride bytes of dynamic
+// shared memory, <= 32 KiB) and copied back out only when the caller asked for the rewritten
+// frames.  entry(L) runs the entry's programs on the lane's row; then the rewritten header is
+// re-parsed and the packet's handle_policy record and flow-group key are written for ingress_run
+// (k_ing_pack fused), and a packet that ended here is counted.
+// CLS_FLAGS: the record's front flags (every GF_PIPE_F_* bit: the top three of the byte) ride
+// along in cls bits 4-6 for k_ing_groups' write-only completion (IngCtx::pout_wo).
+template <int NT, bool CLS_FLAGS, class Entry>
+__device__ __forceinline__ void front_body(const gf_frames &fr, const uint8_t *tc_index, uint32_t vec_copy,
+                                           const uint16_t *slot_of, gf_rec *rec, uint32_t *keys, uint8_t *s6out,
+                                           uint8_t *d6out, gf_pipeline_out *out, uint8_t *snap_out,
+                                           unsigned long long *stats, const gf_key_cfg &K, Entry entry) {
     extern __shared__ uint4 lds_rows[];
     uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
     __shared__ uint32_t sl[272];
@@ -2729,7 +2903,7 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
     {
         const uint8_t *src = fr.snap + (size_t)b0 * S;
         size_t k0 = 0;
-        if (P.vec_copy) {
+        if (vec_copy) {
             const size_t nv = bytes / 16;
             for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
             k0 = nv * 16;
@@ -2743,102 +2917,47 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
     if (i < fr.n) {
         const uint32_t len = fr.len[i];
         const uint32_t cap = S < len ? S : len;
-        Row w{rows + (size_t)threadIdx.x * S, cap};
-        PktHdr h;
-        parse_row(w.p, cap, len, h);
-        const uint32_t et = h.et;
-        const PktHdrA ha{h, flow_hash ? flow_hash[i] : 0u};
-        gf_pipeline_out o{};
-        uint32_t n6[4] = {0, 0, 0, 0};
-        uint32_t sec = 0, ifx = 0, lxc = 0, mapped = 0, ndport = 0;
-        uint32_t ab = 24 + 34;                          // output record, header bytes parsed
-        bool tail = false;
-        do {
-            if (P.has_xdp && xdp_verdict(P.x, ha, len, et, ab) == XDP_DROP_) {
-                o.stage = GF_STAGE_XDP; o.action = XDP_DROP_;
-                break;
-            }
-            if (P.has_lb) {
-                gf_lb_out lo{};
-                uint32_t kd = 0;
-                int ret = TC_OK;
-                bool v6 = false;
-                ab += 12;
-                if (et == 0x86DD) {
-                    if (!(P.L.flags & GF_LB_F_NO_IPV6)) { v6 = true; ab += 28; ret = lb_v6(P.L, ha, len, lo, n6, ab, kd); }
-                } else if (et == 0x0800) {
-                    if (!(P.L.flags & GF_LB_F_NO_IPV4)) ret = lb_v4(P.L, ha, len, lo, ab, kd);
-                }
-                if (ret < 0 || ret == TC_SHOT) {
-                    o.stage = GF_STAGE_LB; o.action = TC_SHOT; o.reason = (uint8_t)(-ret);
-                    n6[0] = n6[1] = n6[2] = n6[3] = 0;
-                    break;
-                }
-                if (ret == TC_REDIRECT) {
-                    pipe_lb_rewrite(w, len, h, v6, lo, n6, kd, ab);
-                    o.slave = lo.slave; o.rev_nat = lo.rev_nat; o.dport = lo.new_dport;
-                    o.daddr4 = v6 ? 0u : lo.new_daddr4;
-                    o.flags |= GF_PIPE_F_LB;
-                    if (P.L.flags & GF_LB_F_REDIRECT) {
-                        o.stage = GF_STAGE_LB; o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)P.lb_redirect_ifindex;
-                        break;
-                    }
-                } else {
-                    n6[0] = n6[1] = n6[2] = n6[3] = 0;
-                }
-            }
-            if (P.tcap_in) {                            // from_netdev's send_trace_notify (bpf_netdev.c:436)
-                uint8_t *d = P.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
-                const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
-                if (P.vec_copy) {
-                    for (uint32_t k = 0; k < cb; k += 16)
-                        *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
-                } else {
-                    for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
-                }
-            }
-            const int r = pipe_netdev(P.nd, w, h, et, len, sec, ifx, lxc, mapped, ndport, ab);
-            if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
-            o.stage = GF_STAGE_NETDEV;
-            if (r == ND_TAILCALL) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; tail = true; }
-            else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
-            else if (r < 0 || r == TC_SHOT) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }
-            else o.action = (uint8_t)r;
-        } while (0);
-        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
+        FrontLane L{};
+        L.i = i; L.len = len;
+        L.w = Row{rows + (size_t)threadIdx.x * S, cap};
+        parse_row(L.w.p, cap, len, L.h);
+        L.et = L.h.et;
+        L.ab = 24 + 34;                                 // output record, header bytes parsed
+        entry(L);
+        // handle_policy's input: the rewritten header, re-parsed
         gf_rec rr;
         uint32_t key;
-        const uint32_t tci = tc_index ? tc_index[i] : 0u;
-        if (tail) {
+        const uint32_t tci = (tc_index ? tc_index[i] : 0u) | L.tci_or;
+        if (L.tail) {
             PktHdr h2;
-            parse_row(w.p, cap, len, h2);
-            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx, slot_of[lxc & 0xffffu],
-                           tci, false, true, h2.s6, h2.d6, rr, K);
-            // the front's record flags (every GF_PIPE_F_* bit: the top three of the byte)
-            // ride along in cls bits 4-6 for k_ing_groups' write-only completion (IngCtx::pout_wo)
-            static_assert(((GF_PIPE_F_ICMP6_TE | GF_PIPE_F_LB | GF_PIPE_F_PORTMAP) & ~0xE0u) == 0,
-                          "the pipeline's front flags must fit the top three bits of the flags byte");
-            rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);
+            parse_row(L.w.p, cap, len, h2);
+            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, L.sec, L.ifx,
+                           slot_of[L.lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr, K);
+            if constexpr (CLS_FLAGS) {
+                static_assert(((GF_PIPE_F_ICMP6_TE | GF_PIPE_F_LB | GF_PIPE_F_PORTMAP) & ~0xE0u) == 0,
+                              "the pipeline's front flags must fit the top three bits of the flags byte");
+                rr.cls |= (uint8_t)(((L.o.flags & 0xE0u) >> 5) << 4);
+            }
             if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
                 reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
                 reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
             }
         } else {
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
+            key = pack_rec(i, L.et, len, 0, 0, 0, 0, 0, 0, L.keep_sec ? L.sec : 0u, 0, 0, tci, true, true, L.h.s6, L.h.d6,
+                           rr, K);
         }
         rec[i] = rr;
         keys[i] = key;
-        out[i] = o;
-        if (nd6) reinterpret_cast<uint4 *>(nd6)[i] = make_uint4(n6[0], n6[1], n6[2], n6[3]);
-        sab = ab;                                       // a tail-called packet: handle_policy counts it
-        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
+        out[i] = L.o;
+        sab = L.ab;                                     // a tail-called packet: handle_policy counts it
+        if (!L.tail) { scnt = true; sreason = L.o.reason; saction = L.o.action; slen = len; }
     }
     if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
     if (snap_out) {
         __syncthreads();
         uint8_t *dst = snap_out + (size_t)b0 * S;
         size_t k0 = 0;
-        if (P.vec_copy) {
+        if (vec_copy) {
             const size_t nv = bytes / 16;
             for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
             k0 = nv * 16;
@@ -2846,6 +2965,92 @@ __global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, 
         for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
     }
     if (stats) st.flush(stats);
+}
+
+// bpf_xdp and bpf_lb from-netdev on the lane's row, ahead of the netdev program (k_pipe_front,
+// k_nd_front).  n6: the LB's new IPv6 daddr, zero unless it translated.  false: the packet
+// ended here and L.o says how.
+__device__ __forceinline__ bool pipe_xdp_lb(const PipeDev &P, FrontLane &L, uint32_t fhash, uint32_t *n6) {
+    const PktHdrA ha{L.h, fhash};
+    gf_pipeline_out &o = L.o;
+    if (P.has_xdp && xdp_verdict(P.x, ha, L.len, L.et, L.ab) == XDP_DROP_) {
+        o.stage = GF_STAGE_XDP; o.action = XDP_DROP_;
+        return false;
+    }
+    if (P.has_lb) {
+        gf_lb_out lo{};
+        uint32_t kd = 0;
+        int ret = TC_OK;
+        bool v6 = false;
+        L.ab += 12;
+        if (L.et == 0x86DD) {
+            if (!(P.L.flags & GF_LB_F_NO_IPV6)) { v6 = true; L.ab += 28; ret = lb_v6(P.L, ha, L.len, lo, n6, L.ab, kd); }
+        } else if (L.et == 0x0800) {
+            if (!(P.L.flags & GF_LB_F_NO_IPV4)) ret = lb_v4(P.L, ha, L.len, lo, L.ab, kd);
+        }
+        if (ret < 0 || ret == TC_SHOT) {
+            o.stage = GF_STAGE_LB; o.action = TC_SHOT; o.reason = (uint8_t)(-ret);
+            n6[0] = n6[1] = n6[2] = n6[3] = 0;
+            return false;
+        }
+        if (ret == TC_REDIRECT) {
+            pipe_lb_rewrite(L.w, L.len, L.h, v6, lo, n6, kd, L.ab);
+            o.slave = lo.slave; o.rev_nat = lo.rev_nat; o.dport = lo.new_dport;
+            o.daddr4 = v6 ? 0u : lo.new_daddr4;
+            o.flags |= GF_PIPE_F_LB;
+            if (P.L.flags & GF_LB_F_REDIRECT) {
+                o.stage = GF_STAGE_LB; o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)P.lb_redirect_ifindex;
+                return false;
+            }
+        } else {
+            n6[0] = n6[1] = n6[2] = n6[3] = 0;
+        }
+    }
+    return true;
+}
+// ... and the packet's nd6 entry
+__device__ __forceinline__ bool front_xdp_lb(const PipeDev &P, FrontLane &L, const uint32_t *flow_hash, uint8_t *nd6) {
+    uint32_t n6[4] = {0, 0, 0, 0};
+    const bool on = pipe_xdp_lb(P, L, flow_hash ? flow_hash[L.i] : 0u, n6);
+    if (nd6) reinterpret_cast<uint4 *>(nd6)[L.i] = make_uint4(n6[0], n6[1], n6[2], n6[3]);
+    return on;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, GF_FRONT_MINW) void k_pipe_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
+                                                      PipeDev P, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
+                                                      uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
+                                                      uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
+    front_body<NT, true>(fr, tc_index, P.vec_copy, slot_of, rec, keys, s6out, d6out, out, snap_out, stats, K,
+                         [&](FrontLane &L) {
+        if (!front_xdp_lb(P, L, flow_hash, nd6)) return;
+        front_capture(L, P.tcap_in, fr.snap_stride, P.vec_copy);   // from_netdev's send_trace_notify (bpf_netdev.c:436)
+        front_result<true>(L, pipe_netdev<false>(P.nd, nullptr, L), GF_STAGE_NETDEV);
+    });
+}
+
+// The pipeline whose netdev stage has GF_NETDEV_F_HANDLE_NS or GF_NETDEV_F_ENCAP; a pipeline
+// that sets neither never gets here.  Not held to k_pipe_front's 64 VGPRs (<= 32 KiB of LDS
+// rows: five blocks per CU).
+template <int NT>
+__global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
+                                                 PipeDev P, NdxDev X, const uint16_t *slot_of, gf_rec *rec,
+                                                 uint32_t *keys, uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
+                                                 uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
+    front_body<NT, true>(fr, tc_index, P.vec_copy, slot_of, rec, keys, s6out, d6out, out, snap_out, stats, K,
+                         [&](FrontLane &L) {
+        if (front_xdp_lb(P, L, flow_hash, nd6)) {
+            front_capture(L, P.tcap_in, fr.snap_stride, P.vec_copy);
+            const int r = pipe_netdev<true>(P.nd, &X, L);
+            const bool respond = r == ND_RESPOND, encap = r == HO_ENCAP;
+            L.o.flags |= respond ? GF_PIPE_F_RESPONDER : encap ? GF_PIPE_F_ENCAP : 0u;
+            L.o.pad0 = (uint8_t)L.call;                 // 0 unless a responder call: action OK, reason 0 (as eg_front6)
+            if (encap) L.o.ifindex_lo = (uint16_t)X.enc.encap_ifindex;
+            L.keep_sec = encap;
+            front_result<true>(L, respond ? TC_OK : encap ? TC_REDIRECT : r, GF_STAGE_NETDEV);
+        }
+        if (X.tunnel_ip) X.tunnel_ip[L.i] = L.tun_ip;
+    });
 }
 
 // ================================================================ from-overlay
@@ -2867,9 +3072,7 @@ template <> struct OvlOpt<true> {
     uint32_t stride;
 };
 struct OvlDev {
-    gf_htab_desc lxc;
-    const uint32_t *lxset;         // cilium_lxc's IPv4 keys: address set + slots (Map::addr_set), or null
-    uint32_t lxbits, lxzero;
+    LxcDev lx;
     uint32_t host_ifindex;         // HOST_IFINDEX, 0 = undefined (to_host is TC_ACT_OK)
     uint32_t host_mac[2], node_mac[2];   // HOST_IFINDEX_MAC, NODE_MAC (LE words)
     uint32_t vec_copy;
@@ -2877,70 +3080,48 @@ struct OvlDev {
 };
 enum { OV_TO_HOST = 1002 };
 
+// to_host (:134-149, :83-98), after ipv4_l3 / ipv6_l3 decremented the TTL
+__device__ __forceinline__ int ovl_to_host(const OvlDev &O, FrontLane &L) {
+    L.w.w32(6, O.node_mac[0]); L.w.w16(10, O.node_mac[1]);   // eth_store_saddr(NODE_MAC)
+    L.w.w32(0, O.host_mac[0]); L.w.w16(4, O.host_mac[1]);    // eth_store_daddr(HOST_IFINDEX_MAC)
+    L.ab += 12;
+    return OV_TO_HOST;
+}
+
 // gw / gl (GENEVE): the first word of the lane's option buffer as skb_get_tunnel_opt leaves it
 // (bytes past options_len zero) and options_len.
 template <bool GENEVE>
-__device__ int ovl_program(const OvlDev &O, Row &w, const PktHdr &h, uint32_t et, uint32_t len, uint32_t &ifx,
-                           uint32_t &lxc, uint32_t &mapped, uint32_t &ndport, uint32_t &ab, uint32_t gw, uint32_t gl) {
-    if (et == 0x0800) {
-        if (len < 34) return D_INVALID;                 // revalidate_data (:114-115)
-        uint32_t kw[5] = {w.r32(30), 0, 0, 0, 1u};      // lookup_ip4_endpoint (:123)
-        const int64_t f = O.lxset ? aset_slot(O.lxset, O.lxbits, O.lxzero, kw[0]) : ht_find<20>(O.lxc, kw, key_hash<20>(kw));
-        ab += 20;
-        if (f < 0) return D_NON_LOCAL;                  // :130-131
-        const uint8_t *ep = ht_val(O.lxc, f);
-        ab += 8;
-        const bool host = gload<uint32_t>(ep + 8) & 1u; // ENDPOINT_F_HOST (:126-127)
-        if (host && !O.host_ifindex) return TC_OK;      // HOST_IFINDEX undefined (:150-151)
-        const uint32_t ttl = w.b(22);                   // ipv4_l3 -> ipv4_dec_ttl (l3.h:54-69, ipv4.h:30-43)
-        if (ttl <= 1) return D_INVALID;
-        l3_csum(w, len, 24, ttl, ttl - 1, 2);
-        w.w8(22, ttl - 1);
-        ab += 3;
-        if (host) {                                     // to_host (:134-149)
-            w.w32(6, O.node_mac[0]); w.w16(10, O.node_mac[1]);   // eth_store_saddr(NODE_MAC)
-            w.w32(0, O.host_mac[0]); w.w16(4, O.host_mac[1]);    // eth_store_daddr(HOST_IFINDEX_MAC)
-            ab += 12;
-            return OV_TO_HOST;
-        }
-        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);   // ipv4_local_delivery (:129)
+__device__ int ovl_program(const OvlDev &O, FrontLane &L, uint32_t gw, uint32_t gl) {
+    if (L.et == 0x0800) {
+        if (L.len < 34) return D_INVALID;               // revalidate_data (:114-115)
+        const uint8_t *ep = lxc_lookup4(O.lx, L.w.r32(30), L.ab);   // lookup_ip4_endpoint (:123)
+        if (!ep) return D_NON_LOCAL;                    // :130-131
+        if (!ep_is_host(ep)) return local_delivery4(L, ep);   // :129
+        if (!O.host_ifindex) return TC_OK;              // HOST_IFINDEX undefined (:150-151)
+        if (const int e = dec_ttl4(L)) return e;        // ipv4_l3 (l3.h:54-69)
+        return ovl_to_host(O, L);
     }
-    if (et == 0x86DD) {
-        if (len < 54) return D_INVALID;                 // :46-47
+    if (L.et == 0x86DD) {
+        if (L.len < 54) return D_INVALID;               // :46-47
         if constexpr (GENEVE) {
             // bpf_skb_get_tunnel_opt (net/core/filter.c): -ENOENT without options, -ENOMEM past the buffer (:60-61)
             if (gl == 0 || gl > 64) return D_NO_TUNNEL_OPT;
-            ab += 1 + 4;
+            L.ab += 1 + 4;
             // parse_geneve_options (:63-65): class 0xffff, type 1, (length & 0x1f) << 2 == 4; r1-r3 ignored
             if ((gw & 0x1fffffffu) != 0x0101ffffu) return D_INVALID_GENEVE;
         }
-        uint32_t kw[5] = {w.r32(38), w.r32(42), w.r32(46), w.r32(50), 2u};   // lookup_ip6_endpoint (:70)
-        const int64_t f = ht_find<20>(O.lxc, kw, key_hash<20>(kw));
-        ab += 20 + 8;
-        if (f < 0) return D_NON_LOCAL;                  // :79-80
-        const uint8_t *ep = ht_val(O.lxc, f);
-        ab += 8;
-        const bool host = gload<uint32_t>(ep + 8) & 1u;
-        if (host && !O.host_ifindex) return TC_OK;      // :99-100
-        const uint32_t hl = w.b(21);                    // ipv6_l3 -> ipv6_dec_hoplimit (l3.h:31-52, ipv6.h:178-193)
-        if (hl <= 1) return ND_ICMP6_TE;
-        w.w8(21, hl - 1);
-        ab += 1;
-        if (host) {                                     // to_host (:83-98)
-            w.w32(6, O.node_mac[0]); w.w16(10, O.node_mac[1]);
-            w.w32(0, O.host_mac[0]); w.w16(4, O.host_mac[1]);
-            ab += 12;
-            return OV_TO_HOST;
-        }
-        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);   // ipv6_local_delivery (:78)
+        const uint8_t *ep = lxc_lookup6(O.lx, L.w, L.ab);   // lookup_ip6_endpoint (:70)
+        if (!ep) return D_NON_LOCAL;                    // :79-80
+        if (!ep_is_host(ep)) return local_delivery6(L, ep);   // :78
+        if (!O.host_ifindex) return TC_OK;              // :99-100
+        if (const int e = dec_hoplimit6(L)) return e;   // ipv6_l3 (l3.h:31-52)
+        return ovl_to_host(O, L);
     }
     return TC_OK;                                       // unknown traffic to the stack (:191-193)
 }
 
-// The sibling of k_pipe_front for the tunnel device: one packet per lane over
-// its frame in LDS (NT * snap_stride bytes of dynamic shared memory, <= 32 KiB:
-// five blocks per CU, so the kernel is not held to k_pipe_front's 64 VGPRs),
-// the handle_policy record and flow-group key written directly for ingress_run.
+// The tunnel device's entry; the source identity is the frame's tunnel id.  Not held to
+// k_pipe_front's 64 VGPRs (<= 32 KiB of LDS rows: five blocks per CU).
 // GENEVE: the lane's option word and options_len are two coalesced column loads issued
 // before the frame-row copy (registers, no LDS); the VXLAN instances compile without them.
 template <int NT, bool GENEVE>
@@ -2949,103 +3130,25 @@ __global__ __launch_bounds__(NT) void k_ovl_front(gf_frames fr, const uint32_t *
                                                   uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
                                                   uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K,
                                                   OvlOpt<GENEVE> G) {
-    extern __shared__ uint4 lds_rows[];
-    uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
-    __shared__ uint32_t sl[272];
-    Stats st{sl};
-    if (stats) st.init();
-    const uint32_t S = fr.snap_stride;
-    const uint32_t b0 = blockIdx.x * NT;
-    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
-    const size_t bytes = (size_t)nb * S;
     uint32_t gw = 0, gl = 0;
     if constexpr (GENEVE) {
-        if (b0 + threadIdx.x < fr.n) {
-            gl = G.len[b0 + threadIdx.x];
-            gw = *reinterpret_cast<const uint32_t *>(G.opt + (size_t)(b0 + threadIdx.x) * G.stride);
+        const uint32_t i = blockIdx.x * NT + threadIdx.x;
+        if (i < fr.n) {
+            gl = G.len[i];
+            gw = *reinterpret_cast<const uint32_t *>(G.opt + (size_t)i * G.stride);
             // the zero-initialised buffer past options_len (gl > 64 is refused before the word is looked at)
             if (gl < 4) gw &= (1u << (8 * gl)) - 1u;
         }
     }
-    {
-        const uint8_t *src = fr.snap + (size_t)b0 * S;
-        size_t k0 = 0;
-        if (O.vec_copy) {
-            const size_t nv = bytes / 16;
-            for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
-            k0 = nv * 16;
-        }
-        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
-    }
-    __syncthreads();
-    const uint32_t i = b0 + threadIdx.x;
-    bool scnt = false;                                  // the lane's counter-block entry
-    uint32_t sreason = 0, saction = 0, slen = 0, sab = 0;
-    if (i < fr.n) {
-        const uint32_t len = fr.len[i];
-        const uint32_t cap = S < len ? S : len;
-        Row w{rows + (size_t)threadIdx.x * S, cap};
-        PktHdr h;
-        parse_row(w.p, cap, len, h);
-        const uint32_t et = h.et;
-        gf_pipeline_out o{};
-        uint32_t ifx = 0, lxc = 0, mapped = 0, ndport = 0;
-        uint32_t ab = 24 + 34 + 4;                      // output record, header bytes parsed, tunnel id
-        if (O.tcap_in) {                                // from_overlay's send_trace_notify (:174): the frame as received
-            uint8_t *d = O.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
-            const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
-            if (O.vec_copy) {
-                for (uint32_t k = 0; k < cb; k += 16)
-                    *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
-            } else {
-                for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
-            }
-        }
-        const int r = ovl_program<GENEVE>(O, w, h, et, len, ifx, lxc, mapped, ndport, ab, gw, gl);
-        if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
-        o.stage = GF_STAGE_OVERLAY;
-        const bool tail = r == ND_TAILCALL;
-        if (tail) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; }
-        else if (r == OV_TO_HOST) { o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)O.host_ifindex; }
-        else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
-        else if (r < 0) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }   // send_drop_notify_error (:159-160, :196-197)
-        else o.action = (uint8_t)r;
-        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
-        gf_rec rr;
-        uint32_t key;
-        const uint32_t tci = tc_index ? tc_index[i] : 0u;
-        if (tail) {
-            PktHdr h2;
-            parse_row(w.p, cap, len, h2);
-            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, tunnel_id[i], ifx,
-                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr, K);
-            rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);   // the front's flags for IngCtx::pout_wo, as k_pipe_front
-            if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
-                reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
-                reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
-            }
-        } else {
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, 0, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
-        }
-        rec[i] = rr;
-        keys[i] = key;
-        out[i] = o;
-        sab = ab;                                       // a tail-called packet: handle_policy counts it
-        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
-    }
-    if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
-    if (snap_out) {
-        __syncthreads();
-        uint8_t *dst = snap_out + (size_t)b0 * S;
-        size_t k0 = 0;
-        if (O.vec_copy) {
-            const size_t nv = bytes / 16;
-            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
-            k0 = nv * 16;
-        }
-        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
-    }
-    if (stats) st.flush(stats);
+    front_body<NT, true>(fr, tc_index, O.vec_copy, slot_of, rec, keys, s6out, d6out, out, snap_out, stats, K,
+                         [&](FrontLane &L) {
+        L.ab += 4;                                      // the tunnel id
+        front_capture(L, O.tcap_in, fr.snap_stride, O.vec_copy);   // from_overlay's send_trace_notify (:174): the frame as received
+        int r = ovl_program<GENEVE>(O, L, gw, gl);
+        if (r == OV_TO_HOST) { r = TC_REDIRECT; L.o.ifindex_lo = (uint16_t)O.host_ifindex; }
+        front_result<false>(L, r, GF_STAGE_OVERLAY);
+        if (L.tail) L.sec = tunnel_id[L.i];
+    });
 }
 
 // encap_and_redirect's bpf_tunnel_key.tunnel_id and GENEVE_OPTS (lib/encap.h:43, 53, 72-81) for
@@ -3081,18 +3184,15 @@ __global__ __launch_bounds__(BLOCK) void k_tun_meta(const uint16_t *lxc_id, cons
 // handle_policy of the same call inserts anything (the inserts are applied after
 // k_ing_groups, see px_log_apply).
 struct HostDev {
-    gf_htab_desc lxc, px4, px6, tunnel;
-    const uint32_t *lxset, *tnset; // cilium_lxc's / the tunnel map's IPv4 keys (Map::addr_set), or null
-    uint32_t lxbits, lxzero, tnbits, tnzero;
+    LxcDev lx;
+    EncapDev enc;
+    gf_htab_desc px4, px6;
     uint32_t flags, fixed_secctx;  // GF_NETDEV_F_*, FIXED_SRC_SECCTX
     uint32_t router6[2];           // first 8 bytes of the netdev's ROUTER_IP (derive_sec_ctx)
-    uint32_t node6[3];             // first 12 bytes of gf_node_cfg.router_ip6 (ipv6_match_prefix_96)
     uint32_t net_mac[2];           // CILIUM_NET_MAC (LE words)
-    uint32_t encap_ifindex, cluster_range, cluster_mask, ipv4_mask;
     uint32_t vec_copy;
     uint8_t *tcap_in;              // TRACE_FROM_HOST / FROM_PROXY captures (128 B per packet; null: no trace)
 };
-enum { HO_ENCAP = 1003 };
 enum { MARK_MAGIC_PROXY_MASK = 0xFFF, MARK_MAGIC_PROXY_INGRESS = 0xFEA, MARK_MAGIC_PROXY_EGRESS = 0xFEB };
 
 // handle_identity_from_proxy (:128-145): the identity the proxy put into the mark
@@ -3152,422 +3252,68 @@ __device__ int host_reverse_proxy(const HostDev &H, Row &w, uint32_t len, bool v
     return 0;
 }
 
-// The ENCAP_IFINDEX branch of handle_ipv4 (:378-393) / handle_ipv6 (:225-243) once the
-// endpoint lookup missed: the cluster-range test and encap_and_redirect's tunnel-map lookup
-// (lib/encap.h:30-70).  true: tun_ip = bpf_tunnel_key.remote_ipv4; false: not in the range, or
-// DROP_NO_TUNNEL_ENDPOINT, which both callers turn into TC_ACT_OK.  Shared with the pipeline's
-// netdev stage (k_nd_front).
-__device__ __forceinline__ bool host_encap4(const HostDev &H, uint32_t da, uint32_t &tun_ip, uint32_t &ab) {
-    if (H.encap_ifindex && (da & H.cluster_mask) == H.cluster_range) {
-        uint32_t tk[5] = {da & H.ipv4_mask, 0, 0, 0, 1u};
-        const int64_t ft = H.tnset ? aset_slot(H.tnset, H.tnbits, H.tnzero, tk[0]) : ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
-        ab += 20;
-        if (ft >= 0) {                                  // encap_and_redirect (lib/encap.h:30-70)
-            tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
-            ab += 20;
-            return true;
-        }
-    }
-    return false;
-}
-__device__ __forceinline__ bool host_encap6(const HostDev &H, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t &tun_ip,
-                                            uint32_t &ab) {
-    if (H.encap_ifindex && d0 == H.node6[0] && d1 == H.node6[1] && d2 == H.node6[2]) {
-        uint32_t tk[5] = {d0, d1, d2, 0u, 2u};          // daddr/96
-        const int64_t ft = ht_find<20>(H.tunnel, tk, key_hash<20>(tk));
-        ab += 20;
-        if (ft >= 0) {
-            tun_ip = __builtin_bswap32(gload<uint32_t>(ht_val(H.tunnel, ft)));
-            ab += 20;
-            return true;
-        }
-    }
-    return false;
-}
-
-__device__ int host_program(const HostDev &H, Row &w, const PktHdr &h, uint32_t et, uint32_t len, uint32_t pid,
-                            uint32_t &sec, uint32_t &rev, uint32_t &tun_ip, uint32_t &ifx, uint32_t &lxc,
-                            uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
-    if (et == 0x0800) {
-        if (len < 34) return D_INVALID;                 // revalidate_data (:337-338)
-        sec = (H.flags & GF_NETDEV_F_FIXED_SECCTX) ? H.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
-        if (pid) sec = pid;                             // :348-349
-        const int rr = host_reverse_proxy(H, w, len, false, h.l4, w.b(23), rev, ab);   // :351
+// pid: the proxy's identity from the mark (0: none)
+__device__ int host_program(const HostDev &H, FrontLane &L, uint32_t pid) {
+    Row &w = L.w;
+    if (L.et == 0x0800) {
+        if (L.len < 34) return D_INVALID;               // revalidate_data (:337-338)
+        L.sec = (H.flags & GF_NETDEV_F_FIXED_SECCTX) ? H.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
+        if (pid) L.sec = pid;                           // :348-349
+        const int rr = host_reverse_proxy(H, w, L.len, false, L.h.l4, w.b(23), L.rev, L.ab);   // :351
         if (rr < 0) return rr;
         w.w32(0, H.net_mac[0]); w.w16(4, H.net_mac[1]); // rewrite_dmac_to_host (:358)
-        ab += 6;
+        L.ab += 6;
         const uint32_t da = w.r32(30);
-        uint32_t kw[5] = {da, 0, 0, 0, 1u};             // lookup_ip4_endpoint (:369)
-        const int64_t f = H.lxset ? aset_slot(H.lxset, H.lxbits, H.lxzero, kw[0]) : ht_find<20>(H.lxc, kw, key_hash<20>(kw));
-        ab += 20;
-        if (f >= 0) {
-            const uint8_t *ep = ht_val(H.lxc, f);
-            ab += 8;
-            if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;   // ENDPOINT_F_HOST (:372-373)
-            const uint32_t ttl = w.b(22);               // ipv4_local_delivery (:375): ipv4_dec_ttl
-            if (ttl <= 1) return D_INVALID;
-            l3_csum(w, len, 24, ttl, ttl - 1, 2);
-            w.w8(22, ttl - 1);
-            ab += 3;
-            return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+        const uint8_t *ep = lxc_lookup4(H.lx, da, L.ab);   // lookup_ip4_endpoint (:369)
+        if (ep) {
+            if (ep_is_host(ep)) return TC_OK;           // :372-373
+            return local_delivery4(L, ep);              // :375
         }
-        if (host_encap4(H, da, tun_ip, ab)) return HO_ENCAP;   // ENCAP_IFINDEX (:378-393)
+        if (host_encap4(H.enc, da, L.tun_ip, L.ab)) return HO_ENCAP;   // ENCAP_IFINDEX (:378-393)
         return TC_OK;                                   // :395
     }
-    if (et == 0x86DD) {
-        if (len < 54) return D_INVALID;                 // :174-175
-        sec = 2u;                                       // derive_sec_ctx (:50-64)
-        if (H.flags & GF_NETDEV_F_FIXED_SECCTX) sec = H.fixed_secctx;
-        else if (w.r32(22) == H.router6[0] && w.r32(26) == H.router6[1])
-            sec = __builtin_bswap32(w.r32(14) & __builtin_bswap32(0x000FFFFFu));
-        if (pid) sec = pid;                             // :195-196
-        const int rr = host_reverse_proxy(H, w, len, true, h.l4, w.b(20), rev, ab);   // :198, ip6->nexthdr
+    if (L.et == 0x86DD) {
+        if (L.len < 54) return D_INVALID;               // :174-175
+        L.sec = derive_sec_ctx6(w, H.flags, H.fixed_secctx, H.router6);
+        if (pid) L.sec = pid;                           // :195-196
+        const int rr = host_reverse_proxy(H, w, L.len, true, L.h.l4, w.b(20), L.rev, L.ab);   // :198, ip6->nexthdr
         if (rr < 0) return rr;
         w.w32(0, H.net_mac[0]); w.w16(4, H.net_mac[1]); // rewrite_dmac_to_host (:205)
-        ab += 6;
-        const uint32_t d0 = w.r32(38), d1 = w.r32(42), d2 = w.r32(46);
-        uint32_t kw[5] = {d0, d1, d2, w.r32(50), 2u};   // lookup_ip6_endpoint (:216)
-        const int64_t f = ht_find<20>(H.lxc, kw, key_hash<20>(kw));
-        ab += 20 + 8;
-        if (f >= 0) {
-            const uint8_t *ep = ht_val(H.lxc, f);
-            ab += 8;
-            if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;   // :219-220
-            const uint32_t hl = w.b(21);                // ipv6_local_delivery (:222): ipv6_dec_hoplimit
-            if (hl <= 1) return ND_ICMP6_TE;
-            w.w8(21, hl - 1);
-            ab += 1;
-            return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
+        L.ab += 6;
+        const uint8_t *ep = lxc_lookup6(H.lx, w, L.ab); // lookup_ip6_endpoint (:216)
+        if (ep) {
+            if (ep_is_host(ep)) return TC_OK;           // :219-220
+            return local_delivery6(L, ep);              // :222
         }
-        if (host_encap6(H, d0, d1, d2, tun_ip, ab)) return HO_ENCAP;   // :225-243
+        if (host_encap6(H.enc, w.r32(38), w.r32(42), w.r32(46), L.tun_ip, L.ab)) return HO_ENCAP;   // :225-243
         return TC_OK;                                   // :245
     }
     return TC_OK;                                       // unknown traffic to the stack (:462-464)
 }
 
-// The sibling of k_ovl_front for cilium_host: one packet per lane over its frame
-// row in LDS (NT * snap_stride bytes of dynamic shared memory, <= 32 KiB), the
-// handle_policy record and flow-group key written directly for ingress_run.  The
-// record keeps GF_PIPE_F_REV_PROXY itself (bit 4 is not among the bits gf_rec.cls
-// carries), so the host side has handle_policy complete the records by
+// cilium_host's entry.  The record keeps GF_PIPE_F_REV_PROXY itself (bit 4 is not among the
+// bits gf_rec.cls carries), so the host side has handle_policy complete the records by
 // read-modify-write (PassArgs::keep_flags) and not write-only.
 template <int NT>
 __global__ __launch_bounds__(NT) void k_host_front(gf_frames fr, const uint32_t *mark, const uint8_t *tc_index,
                                                    HostDev H, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
                                                    uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
                                                    uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
-    extern __shared__ uint4 lds_rows[];
-    uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
-    __shared__ uint32_t sl[272];
-    Stats st{sl};
-    if (stats) st.init();
-    const uint32_t S = fr.snap_stride;
-    const uint32_t b0 = blockIdx.x * NT;
-    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
-    const size_t bytes = (size_t)nb * S;
-    {
-        const uint8_t *src = fr.snap + (size_t)b0 * S;
-        size_t k0 = 0;
-        if (H.vec_copy) {
-            const size_t nv = bytes / 16;
-            for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
-            k0 = nv * 16;
+    front_body<NT, false>(fr, tc_index, H.vec_copy, slot_of, rec, keys, s6out, d6out, out, snap_out, stats, K,
+                          [&](FrontLane &L) {
+        L.ab += 4;                                      // the mark
+        uint32_t skip = 0;
+        const uint32_t pid = host_mark_identity(mark ? mark[L.i] : 0u, skip);   // :425
+        front_capture(L, H.tcap_in, fr.snap_stride, H.vec_copy);   // from_netdev's send_trace_notify (:433): the frame as received
+        int r = host_program(H, L, pid);
+        if (L.rev) { L.o.flags |= GF_PIPE_F_REV_PROXY; skip = 1; }   // :121, :320
+        if (r == HO_ENCAP) {
+            r = TC_REDIRECT; L.o.ifindex_lo = (uint16_t)H.enc.encap_ifindex; L.o.daddr4 = L.tun_ip;
+            L.keep_sec = true;
         }
-        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
-    }
-    __syncthreads();
-    const uint32_t i = b0 + threadIdx.x;
-    bool scnt = false;                                  // the lane's counter-block entry
-    uint32_t sreason = 0, saction = 0, slen = 0, sab = 0;
-    if (i < fr.n) {
-        const uint32_t len = fr.len[i];
-        const uint32_t cap = S < len ? S : len;
-        Row w{rows + (size_t)threadIdx.x * S, cap};
-        PktHdr h;
-        parse_row(w.p, cap, len, h);
-        const uint32_t et = h.et;
-        gf_pipeline_out o{};
-        uint32_t sec = 0, rev = 0, tun_ip = 0, ifx = 0, lxc = 0, mapped = 0, ndport = 0, skip = 0;
-        uint32_t ab = 24 + 34 + 4;                      // output record, header bytes parsed, mark
-        const uint32_t pid = host_mark_identity(mark ? mark[i] : 0u, skip);   // :425
-        if (H.tcap_in) {                                // from_netdev's send_trace_notify (:433): the frame as received
-            uint8_t *d = H.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
-            const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
-            if (H.vec_copy) {
-                for (uint32_t k = 0; k < cb; k += 16)
-                    *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
-            } else {
-                for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
-            }
-        }
-        const int r = host_program(H, w, h, et, len, pid, sec, rev, tun_ip, ifx, lxc, mapped, ndport, ab);
-        if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
-        if (rev) { o.flags |= GF_PIPE_F_REV_PROXY; skip = 1; }   // :121, :320
-        o.stage = GF_STAGE_HOST;
-        const bool tail = r == ND_TAILCALL;
-        if (tail) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; }
-        else if (r == HO_ENCAP) { o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)H.encap_ifindex; o.daddr4 = tun_ip; }
-        else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
-        else if (r < 0) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }   // send_drop_notify_error (:405-406, :446-447)
-        else o.action = (uint8_t)r;
-        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
-        gf_rec rr;
-        uint32_t key;
-        const uint32_t tci = (tc_index ? tc_index[i] : 0u) | skip;
-        if (tail) {
-            PktHdr h2;
-            parse_row(w.p, cap, len, h2);
-            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx,
-                           slot_of[lxc & 0xffffu], tci, false, true, h2.s6, h2.d6, rr, K);
-            if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
-                reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
-                reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
-            }
-        } else {
-            // an encap redirect keeps its secctx in the (skipped) record: TRACE_TO_OVERLAY's label
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, r == HO_ENCAP ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
-        }
-        rec[i] = rr;
-        keys[i] = key;
-        out[i] = o;
-        sab = ab;                                       // a tail-called packet: handle_policy counts it
-        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
-    }
-    if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
-    if (snap_out) {
-        __syncthreads();
-        uint8_t *dst = snap_out + (size_t)b0 * S;
-        size_t k0 = 0;
-        if (H.vec_copy) {
-            const size_t nv = bytes / 16;
-            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
-            k0 = nv * 16;
-        }
-        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
-    }
-    if (stats) st.flush(stats);
-}
-
-// ================================================================ netdev stage with HANDLE_NS / ENCAP_IFINDEX
-// from_netdev as bpf/init.sh builds it for the native device (:179 -DHANDLE_NS; ENCAP_IFINDEX
-// from node_config.h in tunnel mode, :303-304): pipe_netdev with icmp6_handle
-// (bpf_netdev.c:180-186, lib/icmp6.h:380-401) and the encap branches (:225-243, :378-392).
-// A pipeline that sets neither GF_NETDEV_F_HANDLE_NS nor GF_NETDEV_F_ENCAP never gets here.
-struct NdxDev {
-    HostDev enc;                   // the encap state host_encap4 / 6 read: tunnel, tnset, tnbits, tnzero,
-                                   // encap_ifindex, cluster_range / _mask, ipv4_mask, node6 (the rest unset)
-    uint32_t router6[4];           // ROUTER_IP (gf_netdev_cfg.router_ip6): icmp6_handle's echo test
-    uint32_t *tunnel_ip;           // bpf_tunnel_key.remote_ipv4 per frame (0: no encap), or null
-};
-enum { ND_RESPOND = 1004 };
-
-__device__ int pipe_netdev_x(const NetdevDev &N, const NdxDev &X, Row &w, const PktHdr &h, uint32_t et, uint32_t len,
-                             uint32_t &sec, uint32_t &call, uint32_t &tun_ip, uint32_t &ifx, uint32_t &lxc,
-                             uint32_t &mapped, uint32_t &ndport, uint32_t &ab) {
-    const bool encap = N.flags & GF_NETDEV_F_ENCAP;
-    if (et == 0x0800) {
-        if (len < 34) return D_INVALID;                 // revalidate_data
-        sec = (N.flags & GF_NETDEV_F_FIXED_SECCTX) ? N.fixed_secctx : 2u;   // derive_ipv4_sec_ctx: WORLD_ID
-        const uint32_t da = w.r32(30);                  // post-LB daddr
-        uint32_t kw[5] = {da, 0, 0, 0, 1u};             // lookup_ip4_endpoint
-        const int64_t f = N.lxset ? aset_slot(N.lxset, N.lxbits, N.lxzero, kw[0]) : ht_find<20>(N.lxc, kw, key_hash<20>(kw));
-        ab += 20;
-        if (f < 0) {
-            if (encap && host_encap4(X.enc, da, tun_ip, ab)) return HO_ENCAP;   // :378-392
-            return TC_OK;
-        }
-        const uint8_t *ep = ht_val(N.lxc, f);
-        ab += 8;
-        if (gload<uint32_t>(ep + 8) & 1u) return TC_OK; // ENDPOINT_F_HOST
-        const uint32_t ttl = w.b(22);                   // ipv4_dec_ttl, bpf/lib/ipv4.h:30-43
-        if (ttl <= 1) return D_INVALID;
-        l3_csum(w, len, 24, ttl, ttl - 1, 2);
-        w.w8(22, ttl - 1);
-        ab += 3;
-        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
-    }
-    if (et == 0x86DD) {
-        if (len < 54) return D_INVALID;
-        // HANDLE_NS (:180-186): nexthdr as ipv6_hdrlen left it (h.proto: a rejected chain keeps
-        // ip6->nexthdr, never 58).  icmp6_load_type (icmp6.h:38-41) is load_byte at the fixed
-        // ETH_HLEN + 40, also behind extension headers; a load past the frame ends the program
-        // with 0 = TC_ACT_OK.
-        if ((N.flags & GF_NETDEV_F_HANDLE_NS) && h.proto == 58) {
-            if (len < 55) return TC_OK;
-            const uint32_t type = w.b(54);
-            ab += 1;
-            if (type == 135) { call = GF_CALL_ICMP6_NS; return ND_RESPOND; }   // icmp6_handle_ns (:389-390)
-            if (type == 128 && w.r32(38) == X.router6[0] && w.r32(42) == X.router6[1] && w.r32(46) == X.router6[2] &&
-                w.r32(50) == X.router6[3]) {            // :391-393
-                call = GF_CALL_ICMP6_ECHO_REPLY;
-                return ND_RESPOND;
-            }
-        }
-        sec = 2u;                                       // derive_sec_ctx (bpf_netdev.c:50-64)
-        if (N.flags & GF_NETDEV_F_FIXED_SECCTX) sec = N.fixed_secctx;
-        else if (w.r32(22) == N.router6[0] && w.r32(26) == N.router6[1])
-            sec = __builtin_bswap32(w.r32(14) & __builtin_bswap32(0x000FFFFFu));
-        const uint32_t d0 = w.r32(38), d1 = w.r32(42), d2 = w.r32(46);
-        uint32_t kw[5] = {d0, d1, d2, w.r32(50), 2u};
-        const int64_t f = ht_find<20>(N.lxc, kw, key_hash<20>(kw));
-        ab += 20 + 8;
-        if (f < 0) {
-            if (encap && host_encap6(X.enc, d0, d1, d2, tun_ip, ab)) return HO_ENCAP;   // :225-243
-            return TC_OK;
-        }
-        const uint8_t *ep = ht_val(N.lxc, f);
-        ab += 8;
-        if (gload<uint32_t>(ep + 8) & 1u) return TC_OK;
-        const uint32_t hl = w.b(21);                    // ipv6_dec_hoplimit, bpf/lib/ipv6.h:178-193
-        if (hl <= 1) return ND_ICMP6_TE;
-        w.w8(21, hl - 1);
-        ab += 1;
-        return delivery_tail(w, len, h.l4, h.proto, ep, ifx, lxc, mapped, ndport, ab);
-    }
-    return TC_OK;                                       // unknown traffic to the stack
-}
-
-// The sibling of k_pipe_front for a pipeline whose netdev stage has GF_NETDEV_F_HANDLE_NS or
-// GF_NETDEV_F_ENCAP: the same three programs on the lane's LDS row and the same gf_rec / key /
-// record triple, with pipe_netdev_x in place of pipe_netdev.  Like k_ovl_front and k_host_front
-// it is not held to k_pipe_front's 64 VGPRs (<= 32 KiB of LDS rows: five blocks per CU).
-template <int NT>
-__global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc_index, const uint32_t *flow_hash,
-                                                 PipeDev P, NdxDev X, const uint16_t *slot_of, gf_rec *rec,
-                                                 uint32_t *keys, uint8_t *s6out, uint8_t *d6out, gf_pipeline_out *out,
-                                                 uint8_t *nd6, uint8_t *snap_out, unsigned long long *stats, gf_key_cfg K) {
-    extern __shared__ uint4 lds_rows[];
-    uint8_t *rows = reinterpret_cast<uint8_t *>(lds_rows);
-    __shared__ uint32_t sl[272];
-    Stats st{sl};
-    if (stats) st.init();
-    const uint32_t S = fr.snap_stride;
-    const uint32_t b0 = blockIdx.x * NT;
-    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
-    const size_t bytes = (size_t)nb * S;
-    {
-        const uint8_t *src = fr.snap + (size_t)b0 * S;
-        size_t k0 = 0;
-        if (P.vec_copy) {
-            const size_t nv = bytes / 16;
-            for (size_t k = threadIdx.x; k < nv; k += NT) lds_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
-            k0 = nv * 16;
-        }
-        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
-    }
-    __syncthreads();
-    const uint32_t i = b0 + threadIdx.x;
-    bool scnt = false;                                  // the lane's counter-block entry
-    uint32_t sreason = 0, saction = 0, slen = 0, sab = 0;
-    if (i < fr.n) {
-        const uint32_t len = fr.len[i];
-        const uint32_t cap = S < len ? S : len;
-        Row w{rows + (size_t)threadIdx.x * S, cap};
-        PktHdr h;
-        parse_row(w.p, cap, len, h);
-        const uint32_t et = h.et;
-        const PktHdrA ha{h, flow_hash ? flow_hash[i] : 0u};
-        gf_pipeline_out o{};
-        uint32_t n6[4] = {0, 0, 0, 0};
-        uint32_t sec = 0, call = 0, tun_ip = 0, ifx = 0, lxc = 0, mapped = 0, ndport = 0;
-        uint32_t ab = 24 + 34;                          // output record, header bytes parsed
-        bool tail = false, enc = false;
-        do {
-            if (P.has_xdp && xdp_verdict(P.x, ha, len, et, ab) == XDP_DROP_) {
-                o.stage = GF_STAGE_XDP; o.action = XDP_DROP_;
-                break;
-            }
-            if (P.has_lb) {
-                gf_lb_out lo{};
-                uint32_t kd = 0;
-                int ret = TC_OK;
-                bool v6 = false;
-                ab += 12;
-                if (et == 0x86DD) {
-                    if (!(P.L.flags & GF_LB_F_NO_IPV6)) { v6 = true; ab += 28; ret = lb_v6(P.L, ha, len, lo, n6, ab, kd); }
-                } else if (et == 0x0800) {
-                    if (!(P.L.flags & GF_LB_F_NO_IPV4)) ret = lb_v4(P.L, ha, len, lo, ab, kd);
-                }
-                if (ret < 0 || ret == TC_SHOT) {
-                    o.stage = GF_STAGE_LB; o.action = TC_SHOT; o.reason = (uint8_t)(-ret);
-                    n6[0] = n6[1] = n6[2] = n6[3] = 0;
-                    break;
-                }
-                if (ret == TC_REDIRECT) {
-                    pipe_lb_rewrite(w, len, h, v6, lo, n6, kd, ab);
-                    o.slave = lo.slave; o.rev_nat = lo.rev_nat; o.dport = lo.new_dport;
-                    o.daddr4 = v6 ? 0u : lo.new_daddr4;
-                    o.flags |= GF_PIPE_F_LB;
-                    if (P.L.flags & GF_LB_F_REDIRECT) {
-                        o.stage = GF_STAGE_LB; o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)P.lb_redirect_ifindex;
-                        break;
-                    }
-                } else {
-                    n6[0] = n6[1] = n6[2] = n6[3] = 0;
-                }
-            }
-            if (P.tcap_in) {                            // from_netdev's send_trace_notify (bpf_netdev.c:436)
-                uint8_t *d = P.tcap_in + (size_t)i * GF_TRACE_PAYLOAD_LEN;
-                const uint32_t cb = S < GF_TRACE_PAYLOAD_LEN ? S : GF_TRACE_PAYLOAD_LEN;
-                if (P.vec_copy) {
-                    for (uint32_t k = 0; k < cb; k += 16)
-                        *reinterpret_cast<uint4 *>(d + k) = *reinterpret_cast<const uint4 *>(w.p + k);
-                } else {
-                    for (uint32_t k = 0; k < cb; k++) d[k] = w.p[k];
-                }
-            }
-            const int r = pipe_netdev_x(P.nd, X, w, h, et, len, sec, call, tun_ip, ifx, lxc, mapped, ndport, ab);
-            if (mapped) { o.flags |= GF_PIPE_F_PORTMAP; o.dport = (uint16_t)ndport; }
-            o.stage = GF_STAGE_NETDEV;
-            if (r == ND_TAILCALL) { o.stage = GF_STAGE_POLICY; o.lxc_id = (uint16_t)lxc; tail = true; }
-            else if (r == ND_RESPOND) { o.flags |= GF_PIPE_F_RESPONDER; o.pad0 = (uint8_t)call; }   // action OK, reason 0 (as eg_front6)
-            else if (r == HO_ENCAP) {
-                o.action = TC_REDIRECT; o.ifindex_lo = (uint16_t)X.enc.encap_ifindex; o.flags |= GF_PIPE_F_ENCAP;
-                enc = true;
-            }
-            else if (r == ND_ICMP6_TE) { o.action = TC_REDIRECT; o.flags |= GF_PIPE_F_ICMP6_TE; }
-            else if (r < 0 || r == TC_SHOT) { o.action = TC_SHOT; o.reason = (uint8_t)(-r); }
-            else o.action = (uint8_t)r;
-        } while (0);
-        // handle_policy's input: the rewritten header, re-parsed (k_ing_pack fused)
-        gf_rec rr;
-        uint32_t key;
-        const uint32_t tci = tc_index ? tc_index[i] : 0u;
-        if (tail) {
-            PktHdr h2;
-            parse_row(w.p, cap, len, h2);
-            key = pack_rec(i, h2.et, len, h2.sa, h2.da, h2.w0, h2.w3, h2.l4, h2.proto, sec, ifx, slot_of[lxc & 0xffffu],
-                           tci, false, true, h2.s6, h2.d6, rr, K);
-            rr.cls |= (uint8_t)(((o.flags & 0xE0u) >> 5) << 4);   // the front's flags for IngCtx::pout_wo, as k_pipe_front
-            if (h2.et == 0x86DD) {                       // both addresses in one 32-B piece (a6_stride 32)
-                reinterpret_cast<uint4 *>(s6out)[2 * (size_t)i] = make_uint4(h2.s6[0], h2.s6[1], h2.s6[2], h2.s6[3]);
-                reinterpret_cast<uint4 *>(d6out)[2 * (size_t)i] = make_uint4(h2.d6[0], h2.d6[1], h2.d6[2], h2.d6[3]);
-            }
-        } else {
-            // an encap redirect keeps its secctx in the (skipped) record: TRACE_TO_OVERLAY's label
-            key = pack_rec(i, et, len, 0, 0, 0, 0, 0, 0, enc ? sec : 0u, 0, 0, tci, true, true, h.s6, h.d6, rr, K);
-        }
-        rec[i] = rr;
-        keys[i] = key;
-        out[i] = o;
-        if (nd6) reinterpret_cast<uint4 *>(nd6)[i] = make_uint4(n6[0], n6[1], n6[2], n6[3]);
-        if (X.tunnel_ip) X.tunnel_ip[i] = tun_ip;
-        sab = ab;                                       // a tail-called packet: handle_policy counts it
-        if (!tail) { scnt = true; sreason = o.reason; saction = o.action; slen = len; }
-    }
-    if (stats) st.pkt_wave(scnt, sreason, saction, slen, sab);
-    if (snap_out) {
-        __syncthreads();
-        uint8_t *dst = snap_out + (size_t)b0 * S;
-        size_t k0 = 0;
-        if (P.vec_copy) {
-            const size_t nv = bytes / 16;
-            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(dst)[k] = lds_rows[k];
-            k0 = nv * 16;
-        }
-        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) dst[k] = rows[k];
-    }
-    if (stats) st.flush(stats);
+        front_result<false>(L, r, GF_STAGE_HOST);
+        L.tci_or = skip;
+    });
 }
 
 // ---- ingest re-partition (real traffic on N GPUs): the owner rank of each
@@ -7730,6 +7476,98 @@ struct PipeSync {
 };
 static PipeSync &pipe_sync() { static const char tag = 0; return cur_ctx().get<PipeSync>(&tag); }
 
+// ---- what the frame entry points (pipeline, from-overlay, from-host) share on the host
+// The frames and outputs of a classify call: 1 to go on, 0 for an empty batch, or -errno.
+// cols_ok: the output and the entry's own required columns are there.
+static int frames_check(const gf_frames &fr, bool cols_ok) {
+    if (fr.n == 0) return 0;
+    if (!fr.snap || !fr.len || !cols_ok) return -EFAULT;
+    if (fr.snap_stride < 14 || fr.snap_stride > 256) return -EINVAL;   // a header snap, staged in LDS
+    if (fr.n > (1u << 30)) return -E2BIG;
+    return 1;
+}
+
+// A 20-byte-key table's IPv4 keys as an address set, or null (GF_XDP_NOSETS: diagnosis, the hash table)
+static void front_addr_set(const std::shared_ptr<Map> &m, hipStream_t s, const uint32_t *&set, uint32_t &bits,
+                           uint32_t &zero) {
+    if (getenv("GF_XDP_NOSETS") || m->addr_set(20, 8192, s, &set, &bits, &zero)) set = nullptr;
+}
+static LxcDev lxc_dev(const std::shared_ptr<Map> &m, hipStream_t s) {
+    LxcDev d{};
+    d.lxc = m->hdesc();
+    front_addr_set(m, s, d.lxset, d.lxbits, d.lxzero);
+    return d;
+}
+// tun: the node's tunnel map, pushed; without it, or without ENCAP_IFINDEX, nothing is looked up
+static EncapDev encap_dev(const gf_node_cfg &node, const std::shared_ptr<Map> &tun, hipStream_t s) {
+    EncapDev d{};
+    d.encap_ifindex = node.encap_ifindex;
+    if (tun && node.encap_ifindex) {
+        d.tunnel = tun->hdesc();
+        front_addr_set(tun, s, d.tnset, d.tnbits, d.tnzero);
+    }
+    d.cluster_range = node.ipv4_cluster_range; d.cluster_mask = node.ipv4_cluster_mask; d.ipv4_mask = node.ipv4_mask;
+    memcpy(d.node6, node.router_ip6, 12);
+    return d;
+}
+
+// A front kernel's launch: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B
+// (<= 32 KiB of LDS rows), one tile per block
+struct FrontLaunch {
+    uint32_t nt, grid;
+    size_t lds;
+    hipStream_t s;
+    uint8_t *s6, *d6;              // saddr6 | daddr6 per packet in one 32-B piece (IngCtx::a6_stride 32)
+    unsigned long long *sink;
+    gf_key_cfg K;
+};
+template <class Kern, class... A>
+static void launch_nt(Kern k256, Kern k128, const FrontLaunch &f, A... args) {
+    if (f.nt == 256) hipLaunchKernelGGL(k256, dim3(f.grid), dim3(256), f.lds, f.s, args...);
+    else hipLaunchKernelGGL(k128, dim3(f.grid), dim3(128), f.lds, f.s, args...);
+}
+
+// A frame entry point's run, under the caller's locks and after frames_check: the launch
+// geometry, the IPv6 address buffer, the trace set-up, then ingress_run with launch(f, slot_of,
+// rec, keys) as its front.  trace: the program's TR_FROM_* | its stage << 8 when it traces,
+// else 0.  vec_copy / tcap_in: the entry descriptor's fields, set here before the launch.
+template <class Launch>
+static int front_call(const std::shared_ptr<PolicyArray> &policy, const gf_frames &fr, const uint32_t *flow_hash,
+                      uint32_t now_sec, gf_pipeline_out *out, uint8_t *snap_out, hipStream_t s, PassArgs &ta,
+                      uint32_t trace, uint32_t ifindex, uint32_t &vec_copy, uint8_t *&tcap_in, const char *kernel,
+                      Launch launch) {
+    int r;
+    const uint32_t n = fr.n;
+    FrontLaunch f{};
+    f.nt = fr.snap_stride <= 128 ? 256u : 128u;
+    f.grid = (n + f.nt - 1) / f.nt;
+    f.lds = (size_t)f.nt * fr.snap_stride;
+    f.s = s;
+    PipeWs &w = pipe_ws();
+    if (w.s6.bytes < (size_t)n * 32 && (r = w.s6.ensure((size_t)n * 32))) return r;
+    f.s6 = (uint8_t *)w.s6.p; f.d6 = f.s6 + 16;
+    f.sink = (unsigned long long *)stats_sink();
+    f.K = gf_key_for(n, true);
+    vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
+    ta.kind = 1;                                       // records completed as the pipeline's
+    ta.nd_trace = trace;
+    ta.nd_ifindex = ifindex;
+    ta.on = event_ring().records && (ta.nd_trace || array_traces(policy));
+    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
+    if (ta.on && ta.nd_trace) tcap_in = (uint8_t *)trace_ws().in.p;
+    gf_pkt_cols c2{};
+    c2.n = n;
+    c2.saddr6 = f.s6; c2.daddr6 = f.d6;
+    c2.flow_hash = flow_hash;
+    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
+        ProfScope ps(kernel, s);
+        launch(f, slot_of, rec, keys);
+        return hip_ok(hipGetLastError(), kernel);
+    };
+    return ingress_run(policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
+                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+}
+
 extern "C" {
 
 int gf_policy_ingress_classify_batches(int array, uint32_t nb, const gf_pkt_cols *const *batches,
@@ -7845,10 +7683,8 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
     auto p = std::static_pointer_cast<ProgPipe>(o);
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
-    if (fr.n == 0) return 0;
-    if (!fr.snap || !fr.len || !out) return -EFAULT;
-    if (fr.snap_stride < 14) return -EINVAL;
-    if (fr.n > (1u << 30)) return -E2BIG;
+    int r = frames_check(fr, out != nullptr);
+    if (r <= 0) return r;
     hipStream_t s = (hipStream_t)stream;
     HostMarks hm;
     CtxScope cx(s);
@@ -7860,8 +7696,6 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
     lock_array_maps(L, p->policy);
     L.lock();
     CallOrder co(s, L, p->policy.get());
-    int r;
-    const uint32_t n = fr.n;
     PipeDev P{};
     if (p->xdp) {
         auto &x = *p->xdp;
@@ -7886,78 +7720,39 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
         P.has_lb = 1;
     }
     if ((r = push_map(p->lxc, s))) return r;
-    P.nd.lxc = p->lxc->hdesc();
-    if (getenv("GF_XDP_NOSETS") || p->lxc->addr_set(20, 8192, s, &P.nd.lxset, &P.nd.lxbits, &P.nd.lxzero))
-        P.nd.lxset = nullptr;
-    P.nd.flags = p->cfg.netdev.flags;
-    P.nd.fixed_secctx = p->cfg.netdev.fixed_secctx;
-    memcpy(P.nd.router6, p->cfg.netdev.router_ip6, 8);
-    // GF_NETDEV_F_HANDLE_NS / _ENCAP: the sibling front (k_nd_front); neither set: k_pipe_front as ever
-    const bool ndx = p->cfg.netdev.flags & (GF_NETDEV_F_HANDLE_NS | GF_NETDEV_F_ENCAP);
+    const gf_netdev_cfg &nd = p->cfg.netdev;
+    P.nd.lx = lxc_dev(p->lxc, s);
+    P.nd.flags = nd.flags;
+    P.nd.fixed_secctx = nd.fixed_secctx;
+    memcpy(P.nd.router6, nd.router_ip6, 8);
+    // GF_NETDEV_F_HANDLE_NS / _ENCAP: k_nd_front; neither set: k_pipe_front
+    const bool ndx = nd.flags & (GF_NETDEV_F_HANDLE_NS | GF_NETDEV_F_ENCAP);
     NdxDev X{};
     if (ndx) {
-        memcpy(X.router6, p->cfg.netdev.router_ip6, 16);
+        memcpy(X.router6, nd.router_ip6, 16);
         X.tunnel_ip = tunnel_ip;
-        if (p->cfg.netdev.flags & GF_NETDEV_F_ENCAP) {
+        if (nd.flags & GF_NETDEV_F_ENCAP) {
             const gf_node_cfg &node = node_cfg();
             auto tun = node_map(2);
             if (!tun || !node.encap_ifindex) return -EINVAL;   // the node was reconfigured since gf_pipeline_load
             if ((r = push_map(tun, s))) return r;
-            X.enc.tunnel = tun->hdesc();
-            if (getenv("GF_XDP_NOSETS") || tun->addr_set(20, 8192, s, &X.enc.tnset, &X.enc.tnbits, &X.enc.tnzero))
-                X.enc.tnset = nullptr;
-            X.enc.encap_ifindex = node.encap_ifindex;
-            X.enc.cluster_range = node.ipv4_cluster_range; X.enc.cluster_mask = node.ipv4_cluster_mask;
-            X.enc.ipv4_mask = node.ipv4_mask;
-            memcpy(X.enc.node6, node.router_ip6, 12);
+            X.enc = encap_dev(node, tun, s);
         }
     } else if (tunnel_ip) {
-        if (hip_ok(hipMemsetAsync(tunnel_ip, 0, (size_t)n * 4, s), "tunnel_ip")) return -EIO;
+        if (hip_ok(hipMemsetAsync(tunnel_ip, 0, (size_t)fr.n * 4, s), "tunnel_ip")) return -EIO;
     }
-    // LDS staging of the block's frames (one row per lane)
-    // (256 lanes per block up to 128-B snaps, 128 lanes up to 256 B: <= 32 KiB)
-    if (fr.snap_stride > 256) return -EINVAL;          // not a header snap
-    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
-    const size_t lds = (size_t)nt * fr.snap_stride;
-    PipeWs &w = pipe_ws();
-    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
-    if ((r = grow(w.s6, (size_t)n * 32))) return r;    // saddr6 | daddr6 per packet (IngCtx::a6_stride 32)
-    P.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
     PassArgs ta{};
-    ta.kind = 1;
-    ta.nd_trace = (p->cfg.netdev.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_STACK | (GF_STAGE_NETDEV << 8)) : 0u;
-    ta.nd_ifindex = p->cfg.netdev.ingress_ifindex;
-    ta.on = event_ring().records && (ta.nd_trace || array_traces(p->policy));
-    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
-    if (ta.on && ta.nd_trace) P.tcap_in = (uint8_t *)trace_ws().in.p;
-    unsigned long long *sink = (unsigned long long *)stats_sink();
-    const uint32_t grid = (n + nt - 1) / nt;         // one NT-frame tile per block
-    gf_pkt_cols c2{};
-    c2.n = n;
-    c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
-    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
-        if (ndx) {
-            ProfScope ps("k_nd_front", s);
-            if (nt == 256)
-                hipLaunchKernelGGL(k_nd_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tc_index, b->flow_hash, P, X,
-                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
-            else
-                hipLaunchKernelGGL(k_nd_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tc_index, b->flow_hash, P, X,
-                                   slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
-            return hip_ok(hipGetLastError(), "k_nd_front");
-        }
-        ProfScope ps("k_pipe_front", s);
-        if (nt == 256)
-            hipLaunchKernelGGL(k_pipe_front<256>, dim3(grid), dim3(256), lds, s, fr, b->tc_index, b->flow_hash, P,
-                               slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
+    const uint32_t trace = (nd.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_STACK | (GF_STAGE_NETDEV << 8)) : 0u;
+    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, ta, trace, nd.ingress_ifindex, P.vec_copy,
+                      P.tcap_in, ndx ? "k_nd_front" : "k_pipe_front",
+                      [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
+        if (ndx)
+            launch_nt(k_nd_front<256>, k_nd_front<128>, f, fr, b->tc_index, b->flow_hash, P, X, slot_of, rec, keys, f.s6,
+                      f.d6, out, nd6, snap_out, f.sink, f.K);
         else
-            hipLaunchKernelGGL(k_pipe_front<128>, dim3(grid), dim3(128), lds, s, fr, b->tc_index, b->flow_hash, P,
-                               slot_of, rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, nd6, snap_out, sink, gf_key_for(n, true));
-        return hip_ok(hipGetLastError(), "k_pipe_front");
-    };
-    c2.flow_hash = b->flow_hash;
-    return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
-                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+            launch_nt(k_pipe_front<256>, k_pipe_front<128>, f, fr, b->tc_index, b->flow_hash, P, slot_of, rec, keys, f.s6,
+                      f.d6, out, nd6, snap_out, f.sink, f.K);
+    });
 }
 
 // ---- from-overlay ----
@@ -7987,10 +7782,8 @@ static int overlay_call(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts
     const bool geneve = p->cfg.flags & GF_OVERLAY_F_GENEVE;
     if (geneve && !with_opts) return -EINVAL;          // ENCAP_GENEVE reads options: gf_overlay_classify_opts
     const gf_frames &fr = b->frames;
-    if (fr.n == 0) return 0;
-    if (!fr.snap || !fr.len || !out || !b->tunnel_id) return -EFAULT;
-    if (fr.snap_stride < 14 || fr.snap_stride > 256) return -EINVAL;   // a header snap, staged in LDS
-    if (fr.n > (1u << 30)) return -E2BIG;
+    int r = frames_check(fr, out && b->tunnel_id);
+    if (r <= 0) return r;
     OvlOpt<true> G{};
     if (geneve) {                                      // a VXLAN program ignores opts
         if (!opts || !opts->opt || !opts->opt_len) return -EFAULT;
@@ -8007,56 +7800,24 @@ static int overlay_call(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts
     lock_array_maps(L, p->policy);
     L.lock();
     CallOrder co(s, L, p->policy.get());
-    int r;
-    const uint32_t n = fr.n;
     OvlDev O{};
     if ((r = push_map(p->lxc, s))) return r;
-    O.lxc = p->lxc->hdesc();
-    if (getenv("GF_XDP_NOSETS") || p->lxc->addr_set(20, 8192, s, &O.lxset, &O.lxbits, &O.lxzero)) O.lxset = nullptr;
+    O.lx = lxc_dev(p->lxc, s);
     const gf_node_cfg &node = node_cfg();
     O.host_ifindex = node.host_ifindex;
     memcpy(O.host_mac, node.host_mac, 6); memcpy(O.node_mac, node.node_mac, 6);
-    // LDS staging as k_pipe_front: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B (<= 32 KiB)
-    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
-    const size_t lds = (size_t)nt * fr.snap_stride;
-    PipeWs &w = pipe_ws();
-    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
-    if ((r = grow(w.s6, (size_t)n * 32))) return r;    // saddr6 | daddr6 per packet (IngCtx::a6_stride 32)
-    O.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
     PassArgs ta{};
-    ta.kind = 1;                                       // records completed as the pipeline's
-    ta.nd_trace = (p->cfg.flags & GF_OVERLAY_F_TRACE_NOTIFY) ? (TR_FROM_OVERLAY | (GF_STAGE_OVERLAY << 8)) : 0u;
-    ta.nd_ifindex = p->cfg.ingress_ifindex;
-    ta.on = event_ring().records && (ta.nd_trace || array_traces(p->policy));
-    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
-    if (ta.on && ta.nd_trace) O.tcap_in = (uint8_t *)trace_ws().in.p;
-    unsigned long long *sink = (unsigned long long *)stats_sink();
-    const uint32_t grid = (n + nt - 1) / nt;         // one NT-frame tile per block
-    gf_pkt_cols c2{};
-    c2.n = n;
-    c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
-    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
-        ProfScope ps("k_ovl_front", s);
-        if (geneve) {
-            if (nt == 256)
-                hipLaunchKernelGGL((k_ovl_front<256, true>), dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                                   rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true), G);
-            else
-                hipLaunchKernelGGL((k_ovl_front<128, true>), dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                                   rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true), G);
-        } else if (nt == 256)
-            hipLaunchKernelGGL((k_ovl_front<256, false>), dim3(grid), dim3(256), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true),
-                               OvlOpt<false>{});
+    const uint32_t trace = (p->cfg.flags & GF_OVERLAY_F_TRACE_NOTIFY) ? (TR_FROM_OVERLAY | (GF_STAGE_OVERLAY << 8)) : 0u;
+    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, ta, trace, p->cfg.ingress_ifindex, O.vec_copy,
+                      O.tcap_in, "k_ovl_front",
+                      [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
+        if (geneve)
+            launch_nt(k_ovl_front<256, true>, k_ovl_front<128, true>, f, fr, b->tunnel_id, b->tc_index, O, slot_of, rec,
+                      keys, f.s6, f.d6, out, snap_out, f.sink, f.K, G);
         else
-            hipLaunchKernelGGL((k_ovl_front<128, false>), dim3(grid), dim3(128), lds, s, fr, b->tunnel_id, b->tc_index, O, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true),
-                               OvlOpt<false>{});
-        return hip_ok(hipGetLastError(), "k_ovl_front");
-    };
-    c2.flow_hash = b->flow_hash;
-    return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
-                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+            launch_nt(k_ovl_front<256, false>, k_ovl_front<128, false>, f, fr, b->tunnel_id, b->tc_index, O, slot_of, rec,
+                      keys, f.s6, f.d6, out, snap_out, f.sink, f.K, OvlOpt<false>{});
+    });
 }
 
 int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf_pipeline_out *out,
@@ -8121,10 +7882,8 @@ int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipe
     auto p = std::static_pointer_cast<ProgHost>(o);
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
-    if (fr.n == 0) return 0;
-    if (!fr.snap || !fr.len || !out) return -EFAULT;
-    if (fr.snap_stride < 14 || fr.snap_stride > 256) return -EINVAL;   // a header snap, staged in LDS
-    if (fr.n > (1u << 30)) return -E2BIG;
+    int r = frames_check(fr, out != nullptr);
+    if (r <= 0) return r;
     hipStream_t s = (hipStream_t)stream;
     HostMarks hm;
     CtxScope cx(s);
@@ -8136,60 +7895,27 @@ int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipe
     lock_array_maps(L, p->policy);
     L.lock();
     CallOrder co(s, L, p->policy.get());
-    int r;
-    const uint32_t n = fr.n;
     HostDev H{};
     auto px4 = proxy_map(4), px6 = proxy_map(6), tun = node_map(2);
     if ((r = push_map(p->lxc, s)) || (r = push_map(px4, s)) || (r = push_map(px6, s)) || (r = push_map(tun, s))) return r;
-    H.lxc = p->lxc->hdesc();
-    if (getenv("GF_XDP_NOSETS") || p->lxc->addr_set(20, 8192, s, &H.lxset, &H.lxbits, &H.lxzero)) H.lxset = nullptr;
+    const gf_netdev_cfg &nd = p->cfg.netdev;
+    H.lx = lxc_dev(p->lxc, s);
+    H.enc = encap_dev(node_cfg(), tun, s);
     if (px4) H.px4 = px4->hdesc();
     if (px6) H.px6 = px6->hdesc();
-    const gf_node_cfg &node = node_cfg();
-    H.encap_ifindex = node.encap_ifindex;
-    if (tun && node.encap_ifindex) {
-        H.tunnel = tun->hdesc();
-        if (getenv("GF_XDP_NOSETS") || tun->addr_set(20, 8192, s, &H.tnset, &H.tnbits, &H.tnzero)) H.tnset = nullptr;
-    }
-    H.cluster_range = node.ipv4_cluster_range; H.cluster_mask = node.ipv4_cluster_mask; H.ipv4_mask = node.ipv4_mask;
-    memcpy(H.node6, node.router_ip6, 12);
-    H.flags = p->cfg.netdev.flags; H.fixed_secctx = p->cfg.netdev.fixed_secctx;
-    memcpy(H.router6, p->cfg.netdev.router_ip6, 8);
+    H.flags = nd.flags; H.fixed_secctx = nd.fixed_secctx;
+    memcpy(H.router6, nd.router_ip6, 8);
     memcpy(H.net_mac, p->cfg.cilium_net_mac, 6);
-    // LDS staging as k_pipe_front: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B (<= 32 KiB)
-    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
-    const size_t lds = (size_t)nt * fr.snap_stride;
-    PipeWs &w = pipe_ws();
-    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
-    if ((r = grow(w.s6, (size_t)n * 32))) return r;    // saddr6 | daddr6 per packet (IngCtx::a6_stride 32)
-    H.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
     PassArgs ta{};
-    ta.kind = 1;                                       // records completed as the pipeline's
     ta.keep_flags = true;
-    ta.nd_trace = (p->cfg.netdev.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_HOST | (GF_STAGE_HOST << 8)) : 0u;
-    ta.nd_ifindex = p->cfg.netdev.ingress_ifindex;
     ta.hmark = b->mark;
-    ta.on = event_ring().records && (ta.nd_trace || array_traces(p->policy));
-    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
-    if (ta.on && ta.nd_trace) H.tcap_in = (uint8_t *)trace_ws().in.p;
-    unsigned long long *sink = (unsigned long long *)stats_sink();
-    const uint32_t grid = (n + nt - 1) / nt;         // one NT-frame tile per block
-    gf_pkt_cols c2{};
-    c2.n = n;
-    c2.saddr6 = (const uint8_t *)w.s6.p; c2.daddr6 = (const uint8_t *)w.s6.p + 16;
-    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
-        ProfScope ps("k_host_front", s);
-        if (nt == 256)
-            hipLaunchKernelGGL(k_host_front<256>, dim3(grid), dim3(256), lds, s, fr, b->mark, b->tc_index, H, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
-        else
-            hipLaunchKernelGGL(k_host_front<128>, dim3(grid), dim3(128), lds, s, fr, b->mark, b->tc_index, H, slot_of,
-                               rec, keys, (uint8_t *)w.s6.p, (uint8_t *)w.s6.p + 16, out, snap_out, sink, gf_key_for(n, true));
-        return hip_ok(hipGetLastError(), "k_host_front");
-    };
-    c2.flow_hash = b->flow_hash;
-    return ingress_run(p->policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
-                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+    const uint32_t trace = (nd.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_HOST | (GF_STAGE_HOST << 8)) : 0u;
+    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, ta, trace, nd.ingress_ifindex, H.vec_copy,
+                      H.tcap_in, "k_host_front",
+                      [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
+        launch_nt(k_host_front<256>, k_host_front<128>, f, fr, b->mark, b->tc_index, H, slot_of, rec, keys, f.s6, f.d6, out,
+                  snap_out, f.sink, f.K);
+    });
 }
 
 // ---- ingest re-partition ----

@@ -291,6 +291,33 @@ def test_pipeline_fuzz(seed, kw):
     assert dp.dump_map("cilium_proxy6") == p6
 
 
+@pytest.mark.parametrize("stride", [64, 122, 144])
+def test_pipeline_tile_edges(stride):
+    """k_pipe_front's LDS tile at its edges: frames cut to 64 B (256 lanes per block, 16-B
+    copies), 122 B (256 lanes, byte copies) and 144 B (128 lanes), in batches of one packet and
+    of half a tile, a tile and two tiles -1 / +0 / +1, in sequence on one datapath, the
+    rewritten frames requested for every other batch; records, LB v6 addresses, the frames and
+    the CT equal the oracle's."""
+    sc = synth.pipeline_fuzz(seed=31, n_packets=3000, n_batches=1)
+    pk = sc.batches[0]
+    pk = synth.Packets(np.ascontiguousarray(pk.frames[:, :stride]), pk.lens, pk.src_identity, pk.ifindex, pk.lxc_id,
+                       pk.tc_index, pk.flow_hash)
+    dp, ref = Datapath(sc, pin_prefix=None), OracleDP(sc)
+    a = 0
+    for i, n in enumerate((1, 127, 128, 129, 255, 256, 257)):
+        p = pk.slice(a, a + n)
+        a += n
+        out, nd6, snap = dp.pipeline(DeviceBatch(p, parse=False), sc.now + i, snap_out=i % 2 == 0)
+        torch.cuda.synchronize()
+        ro, rn6, rs = ref.pipeline(p, sc.now + i)
+        _cmp_struct(to_numpy(out, PIPE_OUT), ro, f"pipeline stride={stride} n={n}")
+        assert np.array_equal(nd6.cpu().numpy(), rn6), f"pipeline nd6 stride={stride} n={n}"
+        if snap is not None:
+            assert np.array_equal(snap.cpu().numpy(), rs), f"pipeline frames stride={stride} n={n}"
+    for m in ("ct4", "ct6"):
+        assert dp.dump_map(m) == ref.dump(m), m
+
+
 def test_pipeline_dir24_prefilter(monkeypatch):
     """GF_XDP_DIR24=1 through the pipeline's front (k_pipe_front -> xdp_verdict): the
     fuzz pipeline with 400 more v4_dyn prefixes (/22-/31, a 16-bit trie root, so the
