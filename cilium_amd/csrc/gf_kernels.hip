@@ -1471,6 +1471,11 @@ deny:
 #define GF_DBG_DENIED   (1u << 5)   // DBG_POLICY_DENIED
 #define GF_DBG_CREATED  (1u << 6)   // DBG_CT_CREATED4/6 (sent before the map update)
 #define GF_DBG_CAPTURE  (1u << 7)   // the redirect got to DBG_CAPTURE_PROXY_POST (IPv4: + DBG_REV_PROXY_UPDATE)
+// LB_DEBUG (GF_LXC_F_LB_DEBUG; cilium_dbg_lb, lb.h:85-89).  The index looked up is w2; nat->address /
+// nat->port are not logged: the event pass finds them again from w2 (the reverse-NAT maps are
+// host-managed and cannot change inside a call), so the log stays 32 B.
+#define GF_DBG_REVNAT     (1u << 8)   // lb{4,6}_rev_nat was entered: DBG_LB{4,6}_REVERSE_NAT_LOOKUP (lb.h:310, 531)
+#define GF_DBG_REVNAT_HIT (1u << 9)   // the lookup hit, __lb{4,6}_rev_nat ran: DBG_LB{4,6}_REVERSE_NAT (lb.h:264, 456)
 struct DbgLog {
     uint32_t w[8];
     __device__ __forceinline__ void init() {
@@ -1684,6 +1689,7 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
         uint32_t kw[1] = {st.rev_nat};
         int64_t f = ht_find<2>(rn, kw, key_hash<2>(kw));
         ab += 8;
+        if constexpr (DBG) dl->w[0] |= GF_DBG_REVNAT | (f >= 0 ? GF_DBG_REVNAT_HIT : 0u);   // (sent before any check fails)
         if (f >= 0) {
             const uint8_t *nat = ht_val(rn, f);
             int r2 = rev_nat_checks(len, r.l4_off, nh, gload<uint16_t>(nat + 4), r.l4w0, false);
@@ -1791,6 +1797,7 @@ __device__ int ipv6_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
         uint32_t kw[1] = {st.rev_nat};
         int64_t f = ht_find<2>(rn, kw, key_hash<2>(kw));
         ab += 20;
+        if constexpr (DBG) dl->w[0] |= GF_DBG_REVNAT | (f >= 0 ? GF_DBG_REVNAT_HIT : 0u);   // (sent before any check fails)
         if (f >= 0) {
             const uint8_t *nat = ht_val(rn, f);
             int r2 = rev_nat_checks(len, r.l4_off, nh, gload<uint16_t>(nat + 16), r.l4w0, true);
@@ -4270,6 +4277,7 @@ __device__ uint32_t ev_list(const EvSrc &E, uint32_t i, int k, EvOne &out) {
 // debug_capture_msg (24 B: type CILIUM_NOTIFY_DBG_CAPTURE = 3, ..., len_orig, len_cap,
 // arg1, arg2, then len_cap frame bytes).  In EvOne: the header words first, zeros after.
 enum { DBG_GENERIC = 1, DBG_POLICY_DENIED = 5, DBG_CT_MATCH = 8, DBG_CT_VERDICT = 15, DBG_TO_HOST = 19,
+       DBG_LB6_REVERSE_NAT_LOOKUP = 26, DBG_LB6_REVERSE_NAT = 27, DBG_LB4_REVERSE_NAT_LOOKUP = 32, DBG_LB4_REVERSE_NAT = 33,
        DBG_REV_PROXY_UPDATE = 40, DBG_L4_POLICY = 41, DBG_CT_LOOKUP4_1 = 44, DBG_CT_LOOKUP4_2 = 45, DBG_CT_CREATED4 = 46,
        DBG_CT_LOOKUP6_1 = 47, DBG_CT_LOOKUP6_2 = 48, DBG_CT_CREATED6 = 49, DBG_SKIP_PROXY = 50, DBG_L4_CREATE = 51,
        DBG_CAPTURE_PROXY_POST = 9 };
@@ -4289,6 +4297,17 @@ __device__ __forceinline__ EvOne ev_dbg_capture(uint32_t sub, uint32_t source, u
     e.w[4] = a1; e.w[5] = e.w[6] = e.w[7] = 0;
     e.pay = pay; e.pstride = pstride;
     return e;
+}
+// The reverse-NAT entry of index idx (raw be16) in the program's map: {nat->address (IPv6:
+// address.p4), nat->port} as loaded.  Out of line: the probe loop stays out of the event
+// kernels' registers.
+__device__ __attribute__((noinline)) uint2 ev_rev_nat_ol(const gf_lxc_dev *dc, bool v6, uint32_t idx) {
+    const gf_htab_desc rn = gload<gf_htab_desc>(v6 ? &dc->revnat6 : &dc->revnat4);
+    const uint32_t kw[1] = {idx};
+    const int64_t f = ht_find<2>(rn, kw, key_hash<2>(kw));
+    if (f < 0) return make_uint2(0u, 0u);               // (not reached: the running packet found it)
+    const uint8_t *nat = ht_val(rn, f);
+    return make_uint2(gload<uint32_t>(nat + (v6 ? 12 : 0)), gload<uint16_t>(nat + (v6 ? 16 : 4)));
 }
 __device__ __forceinline__ uint32_t ev_ntohs(uint32_t v) { return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu); }
 // ev_list for a plain ingress call (kind 0: handle_policy alone) whose array holds a
@@ -4334,6 +4353,17 @@ __device__ uint32_t ev_list_dbg(const EvSrc &E, uint32_t i, int k, EvOne &out) {
         put(ev_dbg(v6 ? DBG_CT_LOOKUP6_2 : DBG_CT_LOOKUP4_2, lid, hash, ((uint32_t)pr.proto << 8) | tfl, 0));
         if (bits & GF_DBG_MATCH) put(ev_dbg(DBG_CT_MATCH, lid, hash, lw[1], lw[2]));
         put(ev_dbg(DBG_CT_VERDICT, lid, hash, lw[3], lw[2]));
+    }
+    // LB_DEBUG (cilium_dbg_lb is cilium_dbg only with both options, lb.h:85-89, dbg.h:134-233):
+    // lb{4,6}_rev_nat between ct_lookup and policy_can_access_ingress (bpf_lxc.c:801-808, 909-918).
+    // nat->address / nat->port as loaded (be32 / be16; IPv6: address.p4), found again from the
+    // logged index in the program's reverse-NAT map, which no kernel writes.
+    if ((bits & GF_DBG_REVNAT) && (pfl & GF_LXC_F_LB_DEBUG)) {
+        put(ev_dbg(v6 ? DBG_LB6_REVERSE_NAT_LOOKUP : DBG_LB4_REVERSE_NAT_LOOKUP, lid, hash, lw[2], 0));
+        if (bits & GF_DBG_REVNAT_HIT) {
+            const uint2 nat = ev_rev_nat_ol(dc, v6, lw[2]);
+            put(ev_dbg(v6 ? DBG_LB6_REVERSE_NAT : DBG_LB4_REVERSE_NAT, lid, hash, nat.x, nat.y));
+        }
     }
     if (bits & GF_DBG_L4_KEY) put(ev_dbg(DBG_L4_CREATE, lid, hash, pr.src_identity, sec, (lw[4] << 16) | pr.proto));
     if (bits & GF_DBG_L4_PROXY) {                       // l4_proxy_lookup (l4.h:191-216)
@@ -6388,6 +6418,7 @@ int gf_lxc_prog_load(const gf_lxc_cfg *cfg) {
     const bool noct = (cfg->flags & GF_LXC_F_NO_CONNTRACK) != 0;
     if (noct && (cfg->n_l4_ingress || cfg->n_l4_egress)) return -EINVAL;
     if (noct && (cfg->flags & GF_LXC_F_DEBUG)) return -EOPNOTSUPP;   // (the CT-off kernel sends no debug messages)
+    // GF_LXC_F_LB_DEBUG needs no rule: without DEBUG cilium_dbg_lb is the empty cilium_dbg (dbg.h:134-233)
     auto p = std::make_shared<ProgLxc>();
     p->cfg = *cfg;
     if (noct) { p->cfg.ct_map4 = p->cfg.ct_map6 = 0; p->cfg.flags &= ~GF_LXC_F_CT_ACCOUNTING; }

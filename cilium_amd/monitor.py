@@ -68,6 +68,31 @@ def decode(rec):
     return d
 
 
+def _ntohs(x):
+    return ((x & 0xff) << 8) | ((x >> 8) & 0xff)
+
+
+def _ip4(x):
+    return ".".join(str((x >> s) & 0xff) for s in (0, 8, 16, 24))      # a be32 as loaded on a little-endian host
+
+
+def dbg_text(d):
+    """The message part of DebugMsg.Dump (pkg/monitor/datapath_debug.go:279-302) for a decoded
+    type-2 record of one of the load balancer's reverse-NAT subtypes (LB_DEBUG); for every
+    other record, its subtype name."""
+    name = d.get("name", str(d.get("subtype")))
+    if d.get("type") != NOTIFY_DBG_MSG:
+        return name
+    a1, a2 = d["arg1"], d["arg2"]
+    if name in ("DBG_LB6_REVERSE_NAT_LOOKUP", "DBG_LB4_REVERSE_NAT_LOOKUP"):
+        return "Reverse NAT lookup, index=%d" % _ntohs(a1 & 0xffff)
+    if name == "DBG_LB6_REVERSE_NAT":
+        return "Performing reverse NAT, address.p4=%x port=%d" % (a1, _ntohs(a2 & 0xffff))
+    if name == "DBG_LB4_REVERSE_NAT":
+        return "Performing reverse NAT, address=%s port=%d" % (_ip4(a1), _ntohs(a2 & 0xffff))
+    return name
+
+
 def decode_ring(records, count=None):
     """The first `count` slots of a ring (a [capacity, EVENT_RECORD] uint8 array) as dicts."""
     a = np.asarray(records, np.uint8).reshape(-1, EVENT_RECORD)

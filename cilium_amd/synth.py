@@ -20,6 +20,7 @@ NO_PREALLOC = 1
 LB_L3, LB_L4, LB_REDIRECT, LB_NO_IPV4, LB_NO_IPV6 = 1, 2, 4, 8, 16
 LXC_DROP_ALL, LXC_POLICY_INGRESS, LXC_HAVE_L4_POLICY, LXC_CT_ACCOUNTING, LXC_LXC_IPV4 = 1, 2, 4, 8, 16
 LXC_NO_CONNTRACK = 128           # GF_LXC_F_NO_CONNTRACK: the endpoint's Conntrack option disabled
+LXC_LB_DEBUG = 512               # GF_LXC_F_LB_DEBUG: LB_DEBUG, the DebugLB option (pkg/endpoint/endpoint.go:120-124)
 LXC_PRODUCTION = LXC_POLICY_INGRESS | LXC_HAVE_L4_POLICY | LXC_CT_ACCOUNTING | LXC_LXC_IPV4
 TCP, UDP, ICMP, ICMPV6 = 6, 17, 1, 58
 F_FIN, F_SYN, F_RST, F_PSH, F_ACK = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -917,6 +918,19 @@ def conntrack_off(sc, every=1):
             e["l4e"] = []
         off.append(e["lxc_id"])
     return off
+
+
+def lb_debug(sc, lxc_ids=None):
+    """The DebugLB endpoint option (pkg/endpoint/endpoint.go:120-124: LB_DEBUG defined) on
+    the endpoints of the scenario whose lxc_id is listed (None: every one): the program
+    gets GF_LXC_F_LB_DEBUG.  It sends nothing unless the endpoint also has the Debug
+    option (LXC_DEBUG), which this does not change.  Returns the affected lxc_ids."""
+    on = []
+    for e in sc.lxc:
+        if lxc_ids is None or e["lxc_id"] in lxc_ids:
+            e["flags"] |= LXC_LB_DEBUG
+            on.append(e["lxc_id"])
+    return on
 
 
 def pipeline_fuzz(seed=3, n_packets=20000, n_batches=3, lb_redirect=False, fixed_secctx=None, proxy_max=524288):

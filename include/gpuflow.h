@@ -275,8 +275,21 @@ int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out,
                                                gf_overlay_classify* and gf_host_classify run a program that has the flag
                                                exactly as if it were clear.  Together with GF_LXC_F_NO_CONNTRACK:
                                                gf_lxc_prog_load returns -EOPNOTSUPP before anything is bound.  LB_DEBUG
-                                               (the cilium_dbg_lb messages of lb4/6_rev_nat, bpf/lib/lb.h:84-89) is a
-                                               separate option and is not built. */
+                                               (the cilium_dbg_lb messages, bpf/lib/lb.h:84-89) is a separate option:
+                                               GF_LXC_F_LB_DEBUG. */
+#define GF_LXC_F_LB_DEBUG        (1u << 9)  /* LB_DEBUG: the endpoint's DebugLB option (pkg/endpoint/endpoint.go:120-124).
+                                               cilium_dbg_lb is cilium_dbg (bpf/lib/lb.h:85-89), which is empty without
+                                               DEBUG (bpf/lib/dbg.h:134-233): the flag alone is accepted and the program
+                                               runs exactly as without it.  Together with GF_LXC_F_DEBUG,
+                                               gf_policy_ingress_classify(_batches) add the reverse-NAT messages of
+                                               handle_policy (lb4_rev_nat / lb6_rev_nat, bpf_lxc.c:801-808, 909-918) to
+                                               the event ring, see "debug notifications" below; every other entry point
+                                               runs the program as if the flag were clear.  With GF_LXC_F_NO_CONNTRACK
+                                               it needs no rule of its own (DEBUG | NO_CONNTRACK is refused, and without
+                                               DEBUG the flag is inert).  Not built: the cilium_dbg_lb sites of the
+                                               from-container section and of bpf_lb (lb4/6_local's service and slave
+                                               lookups, DBG_PKT_HASH, the loopback SNAT, the egress lb4/6_rev_nat): no
+                                               entry point here sends debug messages for that code. */
 #define GF_MAX_L4_INGRESS 64
 #define GF_MAX_PORTMAP 16
 typedef struct gf_portmap {    /* struct portmap (bpf/lib/common.h), LXC_PORT_MAPPINGS entries */
@@ -849,7 +862,14 @@ int gf_ct_evict_log(int map, gf_ct_evict_rec *out, uint32_t max);
  * (the layouts pkg/monitor/datapath_debug.go DebugMsg / DebugCapture decode).
  * Per packet, in the order sent: DBG_SKIP_PROXY; DBG_CT_LOOKUP4_1/_2 (6_1/_2);
  * at most one DBG_CT_MATCH (the entry's lifetime as stored when the lookup found
- * it, its rev_nat_index); DBG_CT_VERDICT; DBG_L4_CREATE; DBG_GENERIC +
+ * it, its rev_nat_index); DBG_CT_VERDICT; with GF_LXC_F_LB_DEBUG also set, the
+ * reverse NAT (bpf/lib/lb.h:304-316, 524-538; IPv4: a CT_REPLY packet whose
+ * entry has a rev_nat_index and no loopback bit, IPv6: any lookup result whose
+ * entry has a rev_nat_index): DBG_LB4/6_REVERSE_NAT_LOOKUP (the index as stored,
+ * 0), then on a hit DBG_LB4_REVERSE_NAT (nat->address be32, nat->port be16,
+ * lb.h:456) / DBG_LB6_REVERSE_NAT (nat->address.p4, nat->port, lb.h:264), both
+ * before a rewrite that may still end in DROP_CSUM_L4, DROP_WRITE_ERROR or
+ * reverse_map_l4_port's error; DBG_L4_CREATE; DBG_GENERIC +
  * DBG_L4_POLICY (l4_proxy_lookup); DBG_POLICY_DENIED (also for reply / related
  * packets, which pass anyway); DBG_CT_CREATED4/6 (also before
  * DROP_CT_CREATE_FAILED); in the redirect TRACE_TO_PROXY (if traced), then
