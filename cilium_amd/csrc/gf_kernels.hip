@@ -3393,22 +3393,25 @@ struct GcCut {
     uint32_t active;
     uint32_t lru;                 // age key: 0 = lifetime (ctmap.GC), 1 = last use (the LRU stand-in)
 };
+// One bit word of the cluster-start bits (32 slots from slot 32 * w) of table d.
+__device__ __forceinline__ void gc_starts_word(const gf_htab_desc &d, uint32_t *bits, uint64_t w) {
+    uint32_t m = 0;
+    uint64_t i0 = w * 32;
+    uint32_t prev = d.slots[((i0 - 1) & d.mask) * d.slot_size + d.ksz];
+    for (int k = 0; k < 32; k++) {
+        uint64_t i = i0 + k;
+        if (i > d.mask) break;
+        uint32_t st = d.slots[i * d.slot_size + d.ksz];
+        if (st != GF_SLOT_EMPTY && prev == GF_SLOT_EMPTY) m |= 1u << k;
+        prev = st;
+    }
+    bits[w] = m;
+}
 __global__ __launch_bounds__(BLOCK) void k_gc_starts(gf_htab_desc d, uint32_t *bits, const GcCut *cut) {
     if (!cut->active) return;
     const uint64_t nw = (d.mask + 1 + 31) / 32;
-    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t m = 0;
-        uint64_t i0 = w * 32;
-        uint32_t prev = d.slots[((i0 - 1) & d.mask) * d.slot_size + d.ksz];
-        for (int k = 0; k < 32; k++) {
-            uint64_t i = i0 + k;
-            if (i > d.mask) break;
-            uint32_t st = d.slots[i * d.slot_size + d.ksz];
-            if (st != GF_SLOT_EMPTY && prev == GF_SLOT_EMPTY) m |= 1u << k;
-            prev = st;
-        }
-        bits[w] = m;
-    }
+    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * blockDim.x)
+        gc_starts_word(d, bits, w);
 }
 
 __device__ __forceinline__ void gc_move(const gf_htab_desc &d, uint64_t from, uint64_t to, uint32_t vstride) {
@@ -3440,6 +3443,53 @@ __device__ __forceinline__ bool gc_kill(uint32_t lt, uint32_t fl, const GcCut &c
     const unsigned long long cut = (fl & (F_RX_CLOSING | F_TX_CLOSING)) ? c.c : c.o;
     return k < 0 || (unsigned long long)k < cut;
 }
+// The clusters that start in bit word w of table d: every walk stays inside d (it
+// wraps at d.mask and ends at an EMPTY slot of d).
+__device__ __forceinline__ void gc_clusters_word(const gf_htab_desc &d, uint32_t mode, uint32_t lt_off, const GcCut &cut,
+                                                 uint32_t vstride, const uint32_t *bits, uint64_t w, uint32_t &dead,
+                                                 uint32_t &tombs) {
+    uint32_t m = bits[w];
+    while (m) {
+        const int k = __builtin_ctz(m);
+        m &= m - 1;
+        uint64_t j = w * 32 + k;
+        // hole: a slot of this cluster before j was emptied by this walk.  Until
+        // then every slot from the cluster start to j is occupied, so the entry
+        // at j (whose home lies in that range) cannot move: no rehash needed.
+        bool hole = false;
+        for (;;) {
+            uint8_t *sl = d.slots + j * d.slot_size;
+            const uint32_t st = sl[d.ksz];
+            if (st == GF_SLOT_EMPTY) break;
+            if (st == GF_SLOT_TOMB || st == GF_SLOT_FREE) {
+                sl[d.ksz] = GF_SLOT_EMPTY;
+                tombs++;
+                hole = true;
+            } else {
+                const uint8_t *v = ht_val(d, j) + lt_off;
+                const uint32_t lt = *reinterpret_cast<const uint32_t *>(v);
+                const uint32_t fl = *reinterpret_cast<const uint16_t *>(v + 4);
+                if (gc_kill(lt, fl, cut)) {
+                    sl[d.ksz] = GF_SLOT_EMPTY;
+                    dead++;
+                    hole = true;
+                } else if (hole) {
+                    uint32_t kw[10];
+                    for (uint32_t q = 0; q < 10; q++) kw[q] = 0;
+                    for (uint32_t q = 0; q < d.ksz; q += 4) {       // slots are 4-B aligned
+                        const uint32_t x = *reinterpret_cast<const uint32_t *>(sl + q);
+                        kw[q >> 2] = d.ksz - q >= 4 ? x : (x & ((1u << (8 * (d.ksz - q))) - 1u));
+                    }
+                    const uint64_t home = gf_home_slot(gf_key_hash(kw, d.ksz, mode), d.mask, d.slot_size);
+                    for (uint64_t p = home; p != j; p = (p + 1) & d.mask) {
+                        if (d.slots[p * d.slot_size + d.ksz] == GF_SLOT_EMPTY) { gc_move(d, j, p, vstride); break; }
+                    }
+                }
+            }
+            j = (j + 1) & d.mask;
+        }
+    }
+}
 __global__ __launch_bounds__(BLOCK) void k_gc_clusters(gf_htab_desc d, uint32_t mode, uint32_t lt_off, const GcCut *cutp,
                                                        const uint32_t *bits, unsigned long long *res) {
     if (!cutp->active) return;
@@ -3447,51 +3497,68 @@ __global__ __launch_bounds__(BLOCK) void k_gc_clusters(gf_htab_desc d, uint32_t 
     const uint64_t nw = (d.mask + 1 + 31) / 32;
     const uint32_t vstride = d.vals ? (d.sstride ? d.sstride : d.vsz) : 0u;
     uint32_t dead = 0, tombs = 0;
-    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t m = bits[w];
-        while (m) {
-            const int k = __builtin_ctz(m);
-            m &= m - 1;
-            uint64_t j = w * 32 + k;
-            // hole: a slot of this cluster before j was emptied by this walk.  Until
-            // then every slot from the cluster start to j is occupied, so the entry
-            // at j (whose home lies in that range) cannot move: no rehash needed.
-            bool hole = false;
-            for (;;) {
-                uint8_t *sl = d.slots + j * d.slot_size;
-                const uint32_t st = sl[d.ksz];
-                if (st == GF_SLOT_EMPTY) break;
-                if (st == GF_SLOT_TOMB || st == GF_SLOT_FREE) {
-                    sl[d.ksz] = GF_SLOT_EMPTY;
-                    tombs++;
-                    hole = true;
-                } else {
-                    const uint8_t *v = ht_val(d, j) + lt_off;
-                    const uint32_t lt = *reinterpret_cast<const uint32_t *>(v);
-                    const uint32_t fl = *reinterpret_cast<const uint16_t *>(v + 4);
-                    if (gc_kill(lt, fl, cut)) {
-                        sl[d.ksz] = GF_SLOT_EMPTY;
-                        dead++;
-                        hole = true;
-                    } else if (hole) {
-                        uint32_t kw[10];
-                        for (uint32_t q = 0; q < 10; q++) kw[q] = 0;
-                        for (uint32_t q = 0; q < d.ksz; q += 4) {       // slots are 4-B aligned
-                            const uint32_t x = *reinterpret_cast<const uint32_t *>(sl + q);
-                            kw[q >> 2] = d.ksz - q >= 4 ? x : (x & ((1u << (8 * (d.ksz - q))) - 1u));
-                        }
-                        const uint64_t home = gf_home_slot(gf_key_hash(kw, d.ksz, mode), d.mask, d.slot_size);
-                        for (uint64_t p = home; p != j; p = (p + 1) & d.mask) {
-                            if (d.slots[p * d.slot_size + d.ksz] == GF_SLOT_EMPTY) { gc_move(d, j, p, vstride); break; }
-                        }
-                    }
-                }
-                j = (j + 1) & d.mask;
-            }
-        }
-    }
+    for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * blockDim.x)
+        gc_clusters_word(d, mode, lt_off, cut, vstride, bits, w, dead, tombs);
     if (dead) atomicAdd(&res[0], (unsigned long long)dead);
     if (tombs) atomicAdd(&res[1], (unsigned long long)tombs);
+}
+
+// The same sweep over several CT maps at once (gf_ct_gc_maps: a GC round over the
+// per-endpoint maps of the ConntrackLocal option).  Up to GF_GC_MULTI maps travel in the
+// kernel arguments.  The work of a launch is the maps' bit words laid end to end in
+// tiles of BLOCK words, each map's words rounded up to whole tiles, so that a tile
+// lies in one map: t0[k] is map k's first tile and a block finds its tile's map by a
+// scan of t0[] in the arguments (block-uniform, no load from device memory), then
+// runs the one-map bodies on that map's descriptor and its own word index.  The
+// cutoff is a launch argument; each map's {deleted, tombstones cleared} accumulate
+// in its row of the call's result array, and k_gc_end_multi (one thread per map)
+// lowers the map's device count by the deletions and leaves the count in row[2].
+#define GF_GC_MULTI 32u
+struct GcMap {
+    gf_htab_desc d;
+    uint32_t *bits;                     // the map's cluster-start bits (Map::d_gcbits)
+    unsigned long long *res;            // its result row: deleted, tombstones cleared, count after, 0
+    uint32_t mode, lt_off;
+};
+struct GcBatch { GcMap m[GF_GC_MULTI]; uint32_t t0[GF_GC_MULTI + 1]; uint32_t n; };
+static_assert(sizeof(GcBatch) + 64 <= 4096, "the maps travel in the kernel arguments");
+// The map of tile t (t < B.t0[B.n]); k: the block's previous answer (tiles only grow).
+__device__ __forceinline__ uint32_t gc_tile_map(const GcBatch &B, uint32_t t, uint32_t k) {
+    while (t >= B.t0[k + 1]) k++;
+    return k;
+}
+__global__ __launch_bounds__(BLOCK) void k_gc_starts_multi(GcBatch B) {
+    uint32_t k = 0;
+    for (uint32_t t = blockIdx.x; t < B.t0[B.n]; t += gridDim.x) {
+        k = gc_tile_map(B, t, k);
+        const GcMap &M = B.m[k];
+        const uint64_t w = (uint64_t)(t - B.t0[k]) * BLOCK + threadIdx.x;
+        if (w < (M.d.mask + 1 + 31) / 32) gc_starts_word(M.d, M.bits, w);
+    }
+}
+__global__ __launch_bounds__(BLOCK) void k_gc_clusters_multi(GcBatch B, uint32_t filter_time) {
+    const GcCut cut{filter_time, filter_time, 1u, 0u};      // lifetime < filter_time
+    uint32_t k = 0;
+    for (uint32_t t = blockIdx.x; t < B.t0[B.n]; t += gridDim.x) {
+        k = gc_tile_map(B, t, k);
+        const GcMap &M = B.m[k];
+        const uint64_t w = (uint64_t)(t - B.t0[k]) * BLOCK + threadIdx.x;
+        if (w >= (M.d.mask + 1 + 31) / 32) continue;
+        const uint32_t vstride = M.d.vals ? (M.d.sstride ? M.d.sstride : M.d.vsz) : 0u;
+        uint32_t dead = 0, tombs = 0;
+        gc_clusters_word(M.d, M.mode, M.lt_off, cut, vstride, M.bits, w, dead, tombs);
+        if (dead) atomicAdd(&M.res[0], (unsigned long long)dead);
+        if (tombs) atomicAdd(&M.res[1], (unsigned long long)tombs);
+    }
+}
+__global__ void k_gc_end_multi(GcBatch B) {
+    if (threadIdx.x >= B.n) return;
+    const GcMap &M = B.m[threadIdx.x];
+    const unsigned long long dead = M.res[0];
+    const uint32_t c = *M.d.count;
+    const uint32_t after = (unsigned long long)c >= dead ? c - (uint32_t)dead : 0u;
+    *M.d.count = after;
+    M.res[2] = after;
 }
 
 // ---- cilium_proxy{4,6} sweeps (gf_proxy_gc / gf_proxy_cleanup_port; pkg/maps/proxymap:
@@ -8007,32 +8074,37 @@ int gf_pipeline_partition(int pipe, const gf_pipe_batch *b, uint32_t self_rank, 
 }
 
 // ---- conntrack GC ----
+// The test gf_ct_gc and gf_ct_gc_maps apply to a handle's map: a CT map by its sizes.
+static bool ct_gc_accepts(const Map &m) { return !m.is_lpm() && (m.ksz == 14 || m.ksz == 40) && m.vsz == 48; }
+// A map whose host shadow is authoritative (the caller holds its lock): delete there, the
+// replica is rebuilt on the next push.  Returns the entries deleted.
+static bool ct_gc_on_host(const Map &m) { return m.host_valid || !m.dev_valid || !m.d_slots.p; }
+static uint64_t ct_gc_host(Map &m, uint32_t filter_time) {
+    if (m.ht.slots.empty()) return 0;                   // never materialised: no entries
+    const uint32_t lt_off = m.ht.codec == GF_VCODEC_CT ? 0u : 32u;
+    uint64_t dead = 0;
+    std::vector<std::string> keys;
+    uint8_t v[GF_CT_VSZ];
+    for (uint64_t i = 0; i < m.ht.nslots; i++) {
+        if (m.ht.state(i) != GF_SLOT_FULL) continue;
+        m.ht.get_val(i, v);
+        uint32_t lt;
+        memcpy(&lt, v + lt_off, 4);
+        if (lt < filter_time) keys.emplace_back((const char *)m.ht.key(i), m.ksz);
+    }
+    for (auto &k : keys) if (m.erase((const uint8_t *)k.data()) == 0) dead++;
+    return dead;
+}
 int gf_ct_gc(int map, uint32_t filter_time, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
     auto m = get_map(map);
     if (!m) return -EBADF;
-    if (m->is_lpm() || (m->ksz != 14 && m->ksz != 40) || m->vsz != 48) return -EINVAL;
+    if (!ct_gc_accepts(*m)) return -EINVAL;
     hipStream_t s = (hipStream_t)stream;
     CtxScope cx(s);
     std::lock_guard<std::recursive_mutex> mg(m->mu);
     CallOrder co(s, std::vector<OrderPt *>{&m->ord});
-    const uint32_t lt_off = m->ht.codec == GF_VCODEC_CT ? 0u : 32u;
-    if (m->host_valid || !m->dev_valid || !m->d_slots.p) {
-        // host shadow authoritative: delete there, the replica is rebuilt on the next push
-        if (m->ht.slots.empty()) return 0;              // never materialised: no entries
-        uint64_t dead = 0;
-        std::vector<std::string> keys;
-        uint8_t v[GF_CT_VSZ];
-        for (uint64_t i = 0; i < m->ht.nslots; i++) {
-            if (m->ht.state(i) != GF_SLOT_FULL) continue;
-            m->ht.get_val(i, v);
-            uint32_t lt;
-            memcpy(&lt, v + lt_off, 4);
-            if (lt < filter_time) keys.emplace_back((const char *)m->ht.key(i), m->ksz);
-        }
-        for (auto &k : keys) if (m->erase((const uint8_t *)k.data()) == 0) dead++;
-        return (int)std::min<uint64_t>(dead, 0x7fffffff);
-    }
+    if (ct_gc_on_host(*m)) return (int)std::min<uint64_t>(ct_gc_host(*m, filter_time), 0x7fffffff);
     LruDev *L;
     uint32_t *bits;
     int rr;
@@ -8063,6 +8135,100 @@ int gf_ct_gc(int map, uint32_t filter_time, void *stream) {
     m->st_floor = m->lru_seq;
     m->device_modified();
     return (int)std::min<unsigned long long>(r[0], 0x7fffffff);
+}
+
+// One GC round over many CT maps (EnableConntrackGC, pkg/endpointmanager/conntrack.go:84-130:
+// every endpoint's local pair and the global pair): the outcome of gf_ct_gc on each map,
+// with one validation, one set of locks (MapLocks, address order), one CallOrder, and for
+// the device-owned maps GF_GC_MULTI maps per chain of three launches (k_gc_*_multi), the
+// counts fixed on the device and one readback of every map's result row.
+int gf_ct_gc_maps(const int *maps, uint32_t n, uint32_t filter_time, uint32_t *deleted, void *stream) {
+    if (n == 0) return 0;
+    if (!maps) return -EFAULT;
+    if (n > 65536u) return -E2BIG;
+    std::shared_lock<std::shared_mutex> g(prog_lock());
+    std::vector<std::shared_ptr<Map>> ms(n);
+    for (uint32_t k = 0; k < n; k++) {
+        if (!(ms[k] = get_map(maps[k]))) return -EBADF;
+        if (!ct_gc_accepts(*ms[k])) return -EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CtxScope cx(s);
+    MapLocks ml;
+    for (auto &m : ms) ml.add(m);
+    ml.lock();
+    if (ml.held.size() != n) return -EINVAL;            // the same map object twice (lock() drops duplicates)
+    CallOrder co(s, ml);
+    // the device-owned maps' buffers first: a failure here has touched no map
+    std::vector<uint32_t> dev;
+    for (uint32_t k = 0; k < n; k++) {
+        if (ct_gc_on_host(*ms[k])) continue;
+        LruDev *L;
+        uint32_t *bits;
+        int rr;
+        if ((rr = ct_sweep_bufs(*ms[k], L, bits))) return rr;
+        dev.push_back(k);
+    }
+    struct GcWs { DevBuf res; std::vector<unsigned long long> h; };
+    static const char tag = 0;
+    GcWs &w = cur_ctx().get<GcWs>(&tag);
+    const size_t row = 4 * sizeof(unsigned long long);
+    if (!dev.empty() && w.res.bytes < dev.size() * row) {
+        size_t cap = 64;
+        while (cap < dev.size()) cap *= 2;
+        if (w.res.ensure(cap * row)) return -ENOMEM;
+    }
+    std::vector<unsigned long long> cnt(n, 0ull);
+    for (uint32_t k = 0; k < n; k++)
+        if (ct_gc_on_host(*ms[k])) cnt[k] = ct_gc_host(*ms[k], filter_time);
+    if (!dev.empty()) {
+        unsigned long long *res = (unsigned long long *)w.res.p;
+        if (hip_ok(hipMemsetAsync(res, 0, dev.size() * row, s), "gc rows")) return -EIO;
+        {
+            ProfScope ps("k_gc_multi", s);
+            for (size_t b = 0; b < dev.size(); b += GF_GC_MULTI) {
+                GcBatch B{};
+                B.n = (uint32_t)std::min<size_t>(GF_GC_MULTI, dev.size() - b);
+                uint64_t tiles = 0;
+                for (uint32_t j = 0; j < B.n; j++) {
+                    Map &m = *ms[dev[b + j]];
+                    GcMap &M = B.m[j];
+                    M.d = m.hdesc();
+                    M.bits = (uint32_t *)m.d_gcbits.p;
+                    M.res = res + 4 * (b + j);
+                    M.mode = m.ht.mode;
+                    M.lt_off = m.ht.codec == GF_VCODEC_CT ? 0u : 32u;
+                    B.t0[j] = (uint32_t)tiles;
+                    tiles += ((M.d.mask + 1 + 31) / 32 + BLOCK - 1) / BLOCK;
+                }
+                if (tiles > 0xffffffffull) return -E2BIG;   // (2^45 slots: no such tables)
+                B.t0[B.n] = (uint32_t)tiles;
+                const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, 65535u * 8);
+                hipLaunchKernelGGL(k_gc_starts_multi, dim3(grid), dim3(BLOCK), 0, s, B);
+                hipLaunchKernelGGL(k_gc_clusters_multi, dim3(grid), dim3(BLOCK), 0, s, B, filter_time);
+                hipLaunchKernelGGL(k_gc_end_multi, dim3(1), dim3(64), 0, s, B);
+            }
+        }
+        if (hip_ok(hipGetLastError(), "k_gc_multi")) return -EIO;
+        w.h.resize(dev.size() * 4);
+        if (hip_ok(hipMemcpyAsync(w.h.data(), res, dev.size() * row, hipMemcpyDeviceToHost, s), "gc rows back") ||
+            hip_ok(hipStreamSynchronize(s), "gc sync"))
+            return -EIO;
+        for (size_t j = 0; j < dev.size(); j++) {
+            Map &m = *ms[dev[j]];
+            cnt[dev[j]] = w.h[4 * j];
+            m.dev_count_hi = w.h[4 * j + 2];            // exact: k_gc_end_multi left the count there
+            m.ev_pending = 0;
+            m.st_floor = m.lru_seq;
+            m.device_modified();
+        }
+    }
+    unsigned long long sum = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        sum += cnt[k];
+        if (deleted) deleted[k] = (uint32_t)std::min<unsigned long long>(cnt[k], 0xffffffffull);
+    }
+    return (int)std::min<unsigned long long>(sum, 0x7fffffff);
 }
 
 // ---- proxy map GC / redirect-close cleanup ----

@@ -15,6 +15,7 @@ import errno
 import numpy as np
 
 from . import bpf
+from .maps import ctmap
 from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
                    gf_overlay_batch, gf_tunnel_opts, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
@@ -420,6 +421,18 @@ class Datapath:
         """gf_proxy_cleanup_port on the current stream: deletes the TCP entries whose dport is
         `port` (host order here, stored in network order), returns the count."""
         return _check(lib.gf_proxy_cleanup_port(self.fd[name], _be16(port), _stream()), "gf_proxy_cleanup_port")
+
+    # ---- conntrack GC (pkg/endpointmanager/conntrack.go: EnableConntrackGC) ----
+    def ct_gc_round(self, now_sec):
+        """One GC round on the current stream: every CT map the scenario's programs bind
+        (per-endpoint and shared ones, IPv4 and IPv6), each once, in one gf_ct_gc_maps
+        call.  Returns {map name: entries deleted}."""
+        names = []
+        for e in self.sc.lxc or []:
+            for fam in ("ct4", "ct6"):
+                if e.get(fam) and e[fam] not in names:
+                    names.append(e[fam])
+        return dict(zip(names, ctmap.GCMaps([self.fd[n] for n in names], now_sec, _stream())))
 
     # ---- map readback ----------------------------------------------------
     def dump_map(self, name):

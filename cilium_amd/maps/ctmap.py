@@ -6,7 +6,9 @@ CtEntry (48 B): rx_packets, rx_bytes, tx_packets, tx_bytes, lifetime u32, flags 
                 revnat u16 (network order), unused u16, pad u16, src_sec_id u32
 GC (ctmap.go:277-352) deletes entries whose lifetime < now; Flush (:354-368)
 deletes every entry.  Both go to gf_ct_gc: a device sweep of the HBM replica
-(with probe-cluster compaction) when the datapath owns the map.
+(with probe-cluster compaction) when the datapath owns the map.  GCMaps / GCRound
+collect many maps in one gf_ct_gc_maps call: one iteration of the agent's loop over
+every endpoint's local pair and the global pair (pkg/endpointmanager/conntrack.go:84-130).
 """
 import errno
 import struct
@@ -92,3 +94,57 @@ def GC(fd, now_sec, v6=False):
 def Flush(fd, v6=False):
     """ctmap.Flush: GC with filter time MaxTime (every entry)."""
     return GC(fd, MaxTime, v6)
+
+
+def GCMaps(fds, now_sec, stream=None):
+    """GC over many CT maps in one gf_ct_gc_maps call (IPv4 and IPv6, LRU and HASH,
+    host- and device-owned maps mixed; each map at most once).  Returns the number of
+    entries deleted from each map, in the order of `fds`."""
+    import ctypes as C
+    from .._lib import lib
+    fds = [int(f) for f in fds]
+    n = len(fds)
+    arr = (C.c_int * max(n, 1))(*fds)
+    out = (C.c_uint32 * max(n, 1))()
+    rc = lib.gf_ct_gc_maps(arr, n, now_sec & 0xFFFFFFFF, out, stream)
+    if rc < 0:
+        raise bpf.BPFError(-rc, "Unable to garbage collect CT maps")
+    return list(out[:n])
+
+
+def GCRound(endpoints, now_sec, ipv4=True, ipv6=True, open_map=None):
+    """One iteration of the agent's GC loop (EnableConntrackGC,
+    pkg/endpointmanager/conntrack.go:84-130) over `endpoints`, an iterable of
+    (ep_id, conntrack_local): an endpoint with ConntrackLocal contributes its own
+    cilium_ct6_<id> / cilium_ct4_<id> (MapNames), and the global pair is collected
+    once per round however many endpoints share it (seenGlobal).  Every map goes
+    through one GCMaps call.  open_map(name, v6, max_entries) returns the map's
+    handle, which stays the caller's, or None to leave that map out; the default is
+    RunGC's (:64-70): the pinned map is opened, a map that is not there is left out,
+    and the handles are closed after the round.  Returns {map name: deleted}."""
+    own = open_map is None
+
+    def pinned(name, v6, max_entries):
+        try:
+            return bpf.ObjGet(bpf.MapPath(name))
+        except bpf.BPFError:
+            return None
+
+    names, fds, seen_global = [], [], False
+    try:
+        for ep_id, local in endpoints:
+            if not local:
+                if seen_global:
+                    continue
+                seen_global = True
+            name6, name4, size = MapNames(ep_id, local=local)
+            for on, name, v6 in ((ipv6, name6, True), (ipv4, name4, False)):
+                fd = (pinned if own else open_map)(name, v6, size) if on else None
+                if fd is not None:
+                    names.append(name)
+                    fds.append(fd)
+        return dict(zip(names, GCMaps(fds, now_sec)))
+    finally:
+        if own:
+            for fd in fds:
+                bpf.ObjClose(fd)

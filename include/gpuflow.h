@@ -771,6 +771,27 @@ int gf_pipeline_partition(int pipe, const gf_pipe_batch *batch, uint32_t self_ra
  * datapath owns the map (compacting probe clusters in the same sweep), else on the
  * host shadow.  Synchronous on `stream`. */
 int gf_ct_gc(int map, uint32_t filter_time, void *stream);
+/* One GC round over many CT maps in one call: an iteration of the agent's loop
+ * (EnableConntrackGC, pkg/endpointmanager/conntrack.go:84-130), which every 10 s collects
+ * each endpoint's local cilium_ct4_<id> / cilium_ct6_<id> (the ConntrackLocal option) and the
+ * global pair once.  The outcome is exactly that of gf_ct_gc(maps[k], filter_time, stream)
+ * for k = 0..n-1: entries with lifetime < filter_time deleted (0xFFFFFFFF: Flush), probe
+ * clusters compacted, every swept map's element count exact afterwards (a HASH map that was
+ * full takes inserts again).  deleted[k] (host memory, n entries, may be NULL) receives map
+ * k's count; the return value is their sum capped at 0x7fffffff, or -errno.  IPv4 and IPv6
+ * maps, LRU_HASH and HASH maps and both value layouts mix in one array.  A map whose host
+ * shadow is authoritative is collected there, one that never materialised counts 0 (a call
+ * over such maps only launches nothing and needs no device); the device-owned maps are swept
+ * together, 32 per chain of launches whose grid covers all their slots, their counts fixed
+ * on the device, with one readback of all results and one synchronise for the call.
+ * Refused before any map is touched or anything is launched: -EFAULT (maps == NULL with
+ * n > 0), -EBADF (a handle that is not a map), -EINVAL (a map gf_ct_gc refuses: proxy, LPM
+ * and other non-CT maps; or the same map object twice, a second handle from gf_obj_get
+ * included), -E2BIG (n > 65536).  n == 0 returns 0.  Locks every map for the call (address
+ * order, as the classify calls) and is ordered against the calls that use any of them on
+ * other streams.  Synchronous on `stream`. */
+int gf_ct_gc_maps(const int *maps, uint32_t n, uint32_t filter_time,
+                  uint32_t *deleted /* n entries, host memory, may be NULL */, void *stream);
 
 /* ---- proxy map garbage collection and redirect-close cleanup ----
  * For cilium_proxy4 / cilium_proxy6: hash maps with key/value sizes 10/16
