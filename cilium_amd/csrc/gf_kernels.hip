@@ -2375,6 +2375,17 @@ __global__ __launch_bounds__(BLOCK) void k_ing_noct_mark(uint32_t n, const gf_re
     const uint32_t ep = rec[i].ep;
     if (ep && (cfgs[ep - 1].flags & GF_LXC_F_NO_CONNTRACK)) keys[i] = gf_key_skip(K);
 }
+// A HASH CT map that could fill during the batch makes every insert of its family
+// order-dependent (E2BIG for whichever comes last): the family's packets become one
+// bucket, which one lane runs in batch order (fams bit 0: the IPv4 list, which also
+// holds the packets that reach no conntrack; bit 1: IPv6).  Skipped packets stay out.
+__global__ __launch_bounds__(BLOCK) void k_ing_serial_keys(uint32_t n, uint32_t *keys, gf_key_cfg K, uint32_t fams) {
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const uint32_t k = keys[i];
+        if (k == gf_key_skip(K)) continue;
+        if (fams & ((k & K.fam) ? 2u : 1u)) keys[i] = k & K.fam;
+    }
+}
 // One thread per packet in batch order: coalesced record reads and out[i] (or pipeline
 // record, X.pout) writes, the
 // block's counter bins in LDS, policy counters by atomics, no lane state.
@@ -7128,6 +7139,19 @@ static int ct_limits_pct(const CtMaps &cm, uint32_t n, uint32_t per_pkt, hipStre
     return 0;
 }
 
+// After ct_limits: the families (bit 0: IPv4, bit 1: IPv6) with a HASH map the batch could
+// fill.  Such a map fails an insert at exactly max_entries, so which packet fails depends on
+// the order of the inserts: the family runs in batch order (k_ing_serial_keys).  An LRU CT
+// map never fails an insert (its strict mode only keeps the count exact).
+static uint32_t ct_serial_fams(const CtMaps &cm) {
+    uint32_t f = 0;
+    for (auto &m : cm.m4)
+        if (m->type != GF_MAP_TYPE_LRU_HASH && m->dev_count_hi > dev_insert_limit(*m)) f |= 1u;
+    for (auto &m : cm.m6)
+        if (m->type != GF_MAP_TYPE_LRU_HASH && m->dev_count_hi > dev_insert_limit(*m)) f |= 2u;
+    return f;
+}
+
 // ---- CT sweeps on the device: per-map LRU state (histogram, cutoffs, log) and
 // the cluster-start bits of the GC sweep.
 static int ct_sweep_bufs(Map &m, LruDev *&L, uint32_t *&bits) {
@@ -7403,6 +7427,10 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     host_mark("ctlim");
     // 2. group by flow group (records and keys first), 3. longest-first bucket order
     uint32_t n = pkts->n;
+    // A family with a HASH map that could fill: one bucket, in batch order (a schedule
+    // built ahead of the call is rebuilt here)
+    const uint32_t serial = n > 1 && noct != 2 ? ct_serial_fams(cm) : 0u;
+    if (serial) prepared = false;
     Workspace &w = ws();
     if (prepared) {
         // pack + schedule already built in ws() (ingress_prepare)
@@ -7422,6 +7450,12 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     // there is no schedule at all (every program; k_ing_noct alone, below)
     const bool wide = ta && ta->kind == 1;              // the frame fronts' keys (gf_key_for(n, true))
     if (noct == 1 && !prepared && (r = noct_mark(a, n, s, wide))) return r;
+    if (serial) {
+        ProfScope ps("k_ing_serial_keys", s);
+        hipLaunchKernelGGL(k_ing_serial_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, (uint32_t *)w.keys.p,
+                           gf_key_for(n, wide), serial);
+        if ((r = hip_ok(hipGetLastError(), "k_ing_serial_keys"))) return r;
+    }
     if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, ta && ta->kind == 2, wide))) return r;
     host_mark("sched");
     uint32_t *d_sched = (uint32_t *)w.sched.p;

@@ -96,6 +96,18 @@ def Flush(fd, v6=False):
     return GC(fd, MaxTime, v6)
 
 
+def EvictLog(fd, max_records=4096):
+    """gf_ct_evict_log: the LRU stand-in's evictions of a CT map, oldest first, as
+    (seq, now_sec, age_cut, hand_line, lines, evicted) tuples (include/gpuflow.h,
+    gf_ct_evict_rec); at most max_records of them."""
+    from .._lib import lib, gf_ct_evict_rec
+    recs = (gf_ct_evict_rec * max_records)()
+    n = lib.gf_ct_evict_log(fd, recs, max_records)
+    if n < 0:
+        raise bpf.BPFError(-n, "Unable to read the CT map's eviction log")
+    return [(r.seq, r.now_sec, r.age_cut, r.hand_line, r.lines, r.evicted) for r in recs[:min(n, max_records)]]
+
+
 def GCMaps(fds, now_sec, stream=None):
     """GC over many CT maps in one gf_ct_gc_maps call (IPv4 and IPv6, LRU and HASH,
     host- and device-owned maps mixed; each map at most once).  Returns the number of

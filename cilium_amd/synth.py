@@ -669,14 +669,15 @@ def config2(n_flows=16_777_216, n_pairs=1 << 20, n_ep=256, n_ids=4096, n_l3=2000
 
 
 # ------------------------------------------------------------------ parity fuzz scenario
-def fuzz(seed=1, n_packets=20000, n_batches=3, stride=128, ct_max=100000, ct6_max=100000):
+def fuzz(seed=1, n_packets=20000, n_batches=3, stride=128, ct_max=100000, ct6_max=100000, n_ep=16):
     """Small shared pools so that map hits, repeated flows, replies, related
     ICMP, deletes, proxies, rev-NAT, weird IHL, truncation and IPv6
     extension-header chains all occur.  Used by the parity tests (a small
-    ct_max / ct6_max makes the LRU CT maps overflow and exercises eviction)."""
+    ct_max / ct6_max makes the LRU CT maps overflow and exercises eviction).
+    n_ep: the number of endpoints (>= 12; the default's scenarios are fixed: the
+    golden records), their flag sets repeating after the first 16."""
     rng = np.random.default_rng(seed)
     sc = Scenario(f"fuzz{seed}", now=5000)
-    n_ep = 16
     ep4 = (ip4("10.1.0.1") + np.arange(n_ep)).astype(np.uint32)
     ep6 = rand_v6(rng, n_ep, prefix=(0xf0, 0x0d, 0, 0, 0, 0, 0, 0))
     rem4 = np.concatenate([ip4("100.64.1.0") + rng.integers(0, 256, 12), ip4("100.64.2.0") + rng.integers(0, 256, 12),
@@ -803,7 +804,7 @@ def fuzz(seed=1, n_packets=20000, n_batches=3, stride=128, ct_max=100000, ct6_ma
         l4cfg = [(80, 15000 + e, TCP), (53, 0, UDP), (443, 16000, UDP)] if e % 3 == 0 else []
         sc.lxc.append({"lxc_id": int(lxc_id[e]), "seclabel": 256 + e, "policy": f"pol{e}", "ct4": "ct4", "ct6": "ct6",
                        "cidr4": f"cidr4_{e}" if e != 5 else None, "cidr6": f"cidr6_{e}", "revnat4": "revnat4",
-                       "revnat6": "revnat6", "flags": flag_sets[e], "l4": l4cfg})
+                       "revnat6": "revnat6", "flags": flag_sets[e % len(flag_sets)], "l4": l4cfg})
     sc.host_ifindex = 3
 
     # ---- packets

@@ -843,6 +843,27 @@ typedef struct gf_ct_evict_rec {
 } gf_ct_evict_rec;
 /* Copies up to max records (oldest first) and returns the number logged. */
 int gf_ct_evict_log(int map, gf_ct_evict_rec *out, uint32_t max);
+/* Element accounting of a classify call.  Each CT map has an insert limit: the 7/8 load of
+ * the slot array for an LRU CT map (7168 for an ipv4_ct_tuple map of max_entries 700,
+ * 458752 for one of 64000, 229376 for an ipv6_ct_tuple map of 64000), max_entries for a
+ * HASH map.  A pass over n packets is charged per_pkt x n inserts: 2 for handle_policy
+ * (ingress, the pipeline, the deliveries of the other entry points), 3 for the
+ * from-container pass.  While the host's upper bound of the map's count plus that charge
+ * stays within the limit, lanes insert freely and add their net inserts to the count
+ * afterwards.  Otherwise (after the bound was tightened from the last eviction's count,
+ * or read back when the charge alone fits) the family counts every insert exactly, with
+ * an atomic on the count per insert, so that a HASH map fails at exactly max_entries and
+ * an LRU map never overruns its slot array.  An egress batch with an exactly counted
+ * family runs one packet at a time; in a handle_policy pass a family with a HASH map over
+ * its limit runs as one flow group, in batch order, so that the insert that finds the map
+ * full is the one that would in the reference.
+ * With per-endpoint maps (ConntrackLocal) every map of a family is charged the whole
+ * batch, not the packets of its own endpoint, and one map over its limit makes the
+ * family exact for the call.  With the reference's 64000-entry local maps this happens to
+ * an egress batch of more than 458752 / 3 = 152917 packets (LRU; 229376 / 3 = 76458 for
+ * the IPv6 maps) or 64000 / 3 = 21333 packets (HASH) even on empty maps; its deliveries'
+ * handle_policy, charged 2n on top of the 3n, first waits for the device's count from
+ * 458752 / 5 = 91750 (12800) packets on.  Records stay exact; throughput does not. */
 
 /* ---- drop notifications (bpf/lib/drop.h:38-107, DROP_NOTIFY) ----
  * With a ring set, gf_policy_ingress_classify and gf_pipeline_classify append

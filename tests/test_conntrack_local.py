@@ -153,10 +153,14 @@ def test_gpu_conntrack_local_many_maps(n_ep, mx):
 @pytest.mark.parametrize("every,mx", [(1, 500), (2, 800)])
 def test_gpu_conntrack_local_queued_calls(every, mx):
     """Eight calls queued back to back, no host sync between them, on 40 small
-    per-endpoint maps (all or every 2nd endpoint; the rest on the global map): the host's
-    count bound of each map refreshes only from the counts the multi-map eviction pass
-    stamps (`seq << 32 | count`), which may be a call or more behind the host.  Every
-    call's records and every map equal the oracle's once the queue drains."""
+    per-endpoint maps (all or every 2nd endpoint; the rest on the global map).  Every call
+    runs strict: 2 x 20000 inserts are charged to maps whose insert limit is 3584
+    (max_entries 500) or 7168 (800), so the accounting mode never depends on the host's
+    count bound or on the stamps (`seq << 32 | count`) the multi-map eviction pass leaves
+    for it; the queued non-strict case is in test_conntrack_local_pressure.py.  What this
+    checks: the strict per-endpoint kernels and the multi-map pass with the host calls
+    ahead of the device.  Every call's records and every map equal the oracle's once the
+    queue drains."""
     _gpu()
     from cilium_amd.datapath import Datapath, DeviceBatch, ING_OUT, to_numpy
     sc = synth.config2(n_flows=160_000, n_pairs=16_000, n_ep=40, n_ids=512, n_l3=200, n_l4=400, n_wc=8,
