@@ -221,6 +221,8 @@ struct ProgXdp : Obj {
 struct ProgLb : Obj {
     gf_lb_cfg cfg{};
     std::shared_ptr<Map> lb4, lb6;
+    bool has_dstmac = false;       // LB_DSTMAC (gf_lb_prog_set_dstmac; read by gf_lb_classify_frames only)
+    uint8_t dstmac[6] = {};
     ProgLb() : Obj(ObjKind::ProgLb) {}
 };
 struct ProgLxc : Obj {

@@ -3071,6 +3071,111 @@ __global__ __launch_bounds__(NT) void k_nd_front(gf_frames fr, const uint8_t *tc
     });
 }
 
+// ================================================================ bpf_lb over frames
+// from_netdev of bpf/bpf_lb.c:169-212 on a node in lb mode (bpf/init.sh:341-342), where the
+// program is the whole datapath: dispatch on the ethertype, handle_ipv4 / handle_ipv6
+// (lb_v4 / lb_v6, shared with k_lb and the pipeline's LB stage), lb4_xlate / lb6_xlate
+// (pipe_lb_rewrite), LB_DSTMAC (:200-205), the record of gf_lb_classify.  Not on front_body:
+// that skeleton exists to hand a gf_rec, a flow-group key and a pipeline record per frame to
+// ingress_run (60 B a frame), none of which this program has a reader for.  It keeps the
+// skeleton's tile: the block's rows staged in LDS by coalesced 16-B loads, one frame per lane
+// over its row there (DESIGN.md §3 has the reasoning against per-lane global loads).
+// What leaves the tile depends on dst:
+//   null            nothing but the record;
+//   the input rows  (in place) a translated frame's lane stores the fields the program wrote,
+//                   from its LDS row, and nothing else: an untouched frame is not written;
+//   another buffer  the whole tile, patches included, by coalesced 16-B stores.
+struct LbFrDev {
+    uint32_t has_mac, mac_lo, mac_hi;  // LB_DSTMAC as eth_store_daddr writes it: bytes 0-3, 4-5
+    uint32_t vec_copy;
+};
+// bytes [off, off + n) of the lane's row to the same place of its frame in global memory
+// (past the row's cap: dropped, as Row::w8 drops them)
+__device__ __forceinline__ void lbf_put(const Row &w, uint8_t *g, uint32_t off, uint32_t n) {
+    for (uint32_t k = off; k < off + n; k++)
+        if (k < w.cap) g[k] = w.p[k];
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void k_lb_frames(gf_frames fr, const uint32_t *flow_hash, LbDev L, LbFrDev F,
+                                                  gf_lb_out *out, uint8_t *nd6, uint8_t *dst,
+                                                  unsigned long long *stats) {
+    extern __shared__ uint4 lbf_rows[];
+    uint8_t *rows = reinterpret_cast<uint8_t *>(lbf_rows);
+    __shared__ uint32_t sl[272];
+    Stats st{sl};
+    if (stats) st.init();
+    const uint32_t S = fr.snap_stride;
+    const uint32_t b0 = blockIdx.x * NT;
+    const uint32_t nb = fr.n - b0 < NT ? fr.n - b0 : NT;
+    const size_t bytes = (size_t)nb * S;
+    {
+        const uint8_t *src = fr.snap + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (F.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) lbf_rows[k] = reinterpret_cast<const uint4 *>(src)[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) rows[k] = src[k];
+    }
+    __syncthreads();
+    const uint32_t i = b0 + threadIdx.x;
+    const bool act = i < fr.n;
+    const bool inplace = dst == fr.snap;
+    gf_lb_out o{};
+    uint32_t len = 0, ab = 0;
+    if (act) {
+        len = fr.len[i];
+        Row w{rows + (size_t)threadIdx.x * S, S < len ? S : len};
+        PktHdr h;
+        parse_row(w.p, w.cap, len, h);
+        ab = 12 + 34;                                   // output record, header bytes parsed
+        const PktHdrA ha{h, flow_hash ? flow_hash[i] : 0u};
+        uint32_t n6[4] = {0, 0, 0, 0};
+        int ret = TC_OK;
+        bool v6 = false;
+        uint32_t kd = 0;
+        if (h.et == 0x86DD) { if (!(L.flags & GF_LB_F_NO_IPV6)) { v6 = true; ab += 28; ret = lb_v6(L, ha, len, o, n6, ab, kd); } }
+        else if (h.et == 0x0800) { if (!(L.flags & GF_LB_F_NO_IPV4)) ret = lb_v4(L, ha, len, o, ab, kd); }
+        if (ret < 0 || ret == TC_SHOT) {                // send_drop_notify_error(skb, ret, TC_ACT_SHOT)
+            o = gf_lb_out{};
+            o.action = TC_SHOT; o.reason = (uint8_t)(-ret);
+            n6[0] = n6[1] = n6[2] = n6[3] = 0;
+        } else {
+            o.action = ((L.flags & GF_LB_F_REDIRECT) && ret == TC_REDIRECT) ? TC_REDIRECT : TC_OK;
+        }
+        if (ret == TC_REDIRECT && dst) {
+            pipe_lb_rewrite(w, len, h, v6, o, n6, kd, ab);
+            const bool mac = o.action == TC_REDIRECT && F.has_mac;
+            if (mac) { w.w32(0, F.mac_lo); w.w16(4, F.mac_hi); ab += 6; }   // eth_store_daddr(skb, mac.addr, 0)
+            if (inplace) {
+                uint8_t *g = dst + (size_t)i * S;
+                const uint32_t co = csum_l4_offset(h.proto);
+                if (mac) lbf_put(w, g, 0, 6);
+                if (!v6) { lbf_put(w, g, 24, 2); lbf_put(w, g, 30, 4); }
+                else lbf_put(w, g, 38, 16);
+                if (co || v6) lbf_put(w, g, (uint32_t)h.l4 + co, 2);
+                if (o.new_dport) lbf_put(w, g, (uint32_t)h.l4 + 2, 2);
+            }
+        }
+        out[i] = o;
+        if (nd6) reinterpret_cast<uint4 *>(nd6)[i] = make_uint4(n6[0], n6[1], n6[2], n6[3]);
+    }
+    if (stats) st.pkt_wave(act, o.reason, o.action, len, ab);
+    if (dst && !inplace) {
+        __syncthreads();
+        uint8_t *d = dst + (size_t)b0 * S;
+        size_t k0 = 0;
+        if (F.vec_copy) {
+            const size_t nv = bytes / 16;
+            for (size_t k = threadIdx.x; k < nv; k += NT) reinterpret_cast<uint4 *>(d)[k] = lbf_rows[k];
+            k0 = nv * 16;
+        }
+        for (size_t k = k0 + threadIdx.x; k < bytes; k += NT) d[k] = rows[k];
+    }
+    if (stats) st.flush(stats);
+}
+
 // ================================================================ from-overlay
 // from_overlay of bpf/bpf_overlay.c:167-200 -> handle_ipv4 (:106-153) /
 // handle_ipv6 (:38-102), VXLAN (ENCAP_GENEVE undefined), ENABLE_IPV4: the
@@ -7885,6 +7990,72 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
             launch_nt(k_pipe_front<256>, k_pipe_front<128>, f, fr, b->tc_index, b->flow_hash, P, slot_of, rec, keys, f.s6,
                       f.d6, out, nd6, snap_out, f.sink, f.K);
     });
+}
+
+// ---- bpf_lb over frames ----
+int gf_lb_prog_set_dstmac(int prog, const uint8_t mac[6]) {
+    std::unique_lock<std::shared_mutex> g(prog_lock());
+    auto o = get_obj(prog);
+    if (!o || o->kind != ObjKind::ProgLb) return -EBADF;
+    auto p = std::static_pointer_cast<ProgLb>(o);
+    if (!(p->cfg.flags & GF_LB_F_REDIRECT)) return -EINVAL;   // LB_DSTMAC sits inside #ifdef LB_REDIRECT
+    p->has_dstmac = mac != nullptr;
+    if (mac) memcpy(p->dstmac, mac, 6); else memset(p->dstmac, 0, 6);
+    return 0;
+}
+
+int gf_lb_classify_frames(int prog, const gf_frames *frames, const uint32_t *flow_hash, gf_lb_out *out,
+                          uint8_t *nd6, uint8_t *snap_out, void *stream) {
+    std::shared_lock<std::shared_mutex> g(prog_lock());
+    auto o = get_obj(prog);
+    if (!o || o->kind != ObjKind::ProgLb) return -EBADF;
+    auto p = std::static_pointer_cast<ProgLb>(o);
+    if (!frames) return -EFAULT;
+    const gf_frames &fr = *frames;
+    int r = frames_check(fr, out != nullptr);
+    if (r <= 0) return r;
+    hipStream_t s = (hipStream_t)stream;
+    CtxScope cx(s);
+    MapLocks ML;
+    ML.add(p->lb4); ML.add(p->lb6);
+    ML.lock();
+    CallOrder co(s, ML);
+    if ((r = push_map(p->lb4, s)) || (r = push_map(p->lb6, s))) return r;
+    LbDev L{};
+    if (p->lb4) L.s4 = p->lb4->hdesc();
+    if (p->lb6) L.s6 = p->lb6->hdesc();
+    L.flags = p->cfg.flags;
+    LbFrDev F{};
+    if (p->has_dstmac) {
+        F.has_mac = 1;
+        memcpy(&F.mac_lo, p->dstmac, 4);
+        F.mac_hi = (uint32_t)p->dstmac[4] | ((uint32_t)p->dstmac[5] << 8);
+    }
+    F.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
+    // 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B (<= 32 KiB of LDS rows), as the fronts
+    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
+    const uint32_t grid = (fr.n + nt - 1) / nt;
+    const size_t lds = (size_t)nt * fr.snap_stride;
+    {
+        ProfScope ps("k_lb_frames", s);
+        if (nt == 256)
+            hipLaunchKernelGGL(k_lb_frames<256>, dim3(grid), dim3(256), lds, s, fr, flow_hash, L, F, out, nd6, snap_out,
+                               (unsigned long long *)stats_sink());
+        else
+            hipLaunchKernelGGL(k_lb_frames<128>, dim3(grid), dim3(128), lds, s, fr, flow_hash, L, F, out, nd6, snap_out,
+                               (unsigned long long *)stats_sink());
+        if ((r = hip_ok(hipGetLastError(), "k_lb_frames"))) return r;
+    }
+    // send_drop_notify_error's records (bpf_lb.c:194-195): the drop list of ev_list without a trace.
+    // gf_lb_out has no stage byte; a SHOT record is zero past its reason, so byte 2 reads as
+    // GF_STAGE_NONE, which ev_list gives the caller's record: zeros for source, labels and ifindex,
+    // as for GF_STAGE_LB.
+    EvSrc E{};
+    E.recs = (const uint8_t *)out;
+    E.stride = sizeof(gf_lb_out); E.act_off = 0; E.stage_off = 2;
+    E.len = fr.len; E.flow_hash = flow_hash; E.n = fr.n;
+    E.snap = snap_out ? snap_out : fr.snap; E.snap_stride = fr.snap_stride;
+    return emit_drop_events(E, s);
 }
 
 // ---- from-overlay ----

@@ -178,6 +178,9 @@ class Datapath:
         if sc.lb:
             cfg = gf_lb_cfg(h(sc.lb.get("lb4")), h(sc.lb.get("lb6")), sc.lb["flags"], sc.lb.get("redirect_ifindex", 0))
             self.lb_prog = _check(lib.gf_lb_prog_load(C.byref(cfg)), "gf_lb_prog_load")
+            if sc.lb.get("dstmac") is not None:             # LB_DSTMAC (bpf_lb.c:200-205)
+                _check(lib.gf_lb_prog_set_dstmac(self.lb_prog, (C.c_uint8 * 6)(*sc.lb["dstmac"])),
+                       "gf_lb_prog_set_dstmac")
         if sc.lxc:
             self.policy_array = _check(lib.gf_policy_array_create(), "gf_policy_array_create")
             self.lxc_progs = []
@@ -239,6 +242,29 @@ class Datapath:
         c = b.cols()
         _check(lib.gf_lb_classify(self.lb_prog, C.byref(c), _ptr(out), _ptr(nd6), _stream()), "gf_lb_classify")
         return out, nd6
+
+    def lb_frames(self, b, snap_out=True):
+        """gf_lb_classify_frames: bpf_lb's from-netdev over the batch's frames.  snap_out: True = a
+        fresh buffer, False = records only (NULL), "inplace" = b.frames itself, or a tensor of
+        b.frames' shape.  Returns (records [n,12] u8, new_daddr6 [n,16] u8, frames as the program
+        left them [n,stride] u8 or None)."""
+        torch = _torch()
+        out = torch.empty((b.n, 12), dtype=torch.uint8, device=b.device)
+        nd6 = torch.empty((b.n, 16), dtype=torch.uint8, device=b.device)
+        if snap_out is True:
+            snap = torch.empty_like(b.frames)
+        elif snap_out is False or snap_out is None:
+            snap = None
+        elif isinstance(snap_out, str):
+            assert snap_out == "inplace"
+            snap = b.frames
+        else:
+            snap = snap_out
+        stride = b.frames.shape[1] if b.n else 64
+        fr = gf_frames(b.n, stride, _ptr(b.frames), _ptr(b.len))
+        _check(lib.gf_lb_classify_frames(self.lb_prog, C.byref(fr), _ptr(b.flow_hash), _ptr(out), _ptr(nd6), _ptr(snap),
+                                         _stream()), "gf_lb_classify_frames")
+        return out, nd6, snap
 
     def ingress(self, b, now, out=None):
         torch = _torch()

@@ -68,7 +68,7 @@ class Scenario:
     name: str
     maps: dict = field(default_factory=dict)
     xdp: dict = None             # role -> map name
-    lb: dict = None              # {'lb4','lb6','flags','redirect_ifindex'}
+    lb: dict = None              # {'lb4','lb6','flags','redirect_ifindex'[,'dstmac': 6 bytes = LB_DSTMAC]}
     lxc: list = field(default_factory=list)   # endpoint program configs
     netdev: dict = None          # bpf_netdev config of the full pipeline (gf_netdev_cfg)
     node: dict = None            # node_config.h values beyond HOST_IFINDEX (gf_node_cfg): proxy maps, ...
@@ -1010,6 +1010,32 @@ def pipeline_fuzz(seed=3, n_packets=20000, n_batches=3, lb_redirect=False, fixed
                "host_ip6": bytes([0xbe, 0xef, 0, 0, 0, 0, 0, 0, 0, 0, 0xa, 0, 0x2, 0xf, 0xff, 0xff]),
                "host_mac": bytes([0xce, 0x72, 0xa7, 0x03, 0x88, 0x56]),
                "node_mac": bytes([0xde, 0xad, 0xbe, 0xef, 0xc0, 0xde])}
+    return sc
+
+
+def lb_frames_fuzz(seed=3, n_packets=20000, n_batches=3, redirect=True, dstmac=None, to_vip=0.9):
+    """A node in lb mode (bpf/init.sh:341-342): bpf_lb alone over pipeline_fuzz's frames, no
+    XDP program in front of it.  to_vip: the share of the IPv4 / IPv6 frames whose destination
+    is moved onto a service address (the L3-fallback VIP, the one that misses a slave and the
+    one whose master has count 0 included), so that most of a batch is load-balanced traffic.
+    dstmac: 6 bytes = LB_DSTMAC (needs redirect).  The netdev stage stays configured, so the
+    same scenario also loads as a pipeline."""
+    sc = pipeline_fuzz(seed, n_packets, n_batches, lb_redirect=redirect)
+    sc.name = f"lbfr{seed}"
+    sc.xdp = None
+    if dstmac is not None:
+        sc.lb = dict(sc.lb, dstmac=bytes(dstmac))
+    rng = np.random.default_rng(seed ^ 0x1b1b)
+    vip4 = np.unique(sc.maps["lb4_svc"].keys[:, :4], axis=0)
+    vip6 = np.unique(sc.maps["lb6_svc"].keys[:, :16], axis=0)
+    for pk in sc.batches:
+        f = pk.frames
+        et = (f[:, 12].astype(np.uint32) << 8) | f[:, 13]
+        pick = rng.random(pk.n) < to_vip
+        r4 = np.nonzero((et == 0x0800) & pick)[0]
+        f[r4, 30:34] = vip4[rng.integers(0, len(vip4), len(r4))]
+        r6 = np.nonzero((et == 0x86DD) & pick)[0]
+        f[r6, 38:54] = vip6[rng.integers(0, len(vip6), len(r6))]
     return sc
 
 

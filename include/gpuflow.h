@@ -30,6 +30,7 @@
  *     program over one batch of packets that is resident in HBM.
  *     gf_xdp_classify            <- xdp_start/check_filters   bpf/bpf_xdp.c:88-184
  *     gf_lb_classify             <- from_netdev (bpf_lb)      bpf/bpf_lb.c:58-212
+ *     gf_lb_classify_frames      <- the same over raw frames, with lb*_xlate's rewrites and LB_DSTMAC
  *     gf_policy_ingress_classify <- handle_policy/ipv{4,6}_policy bpf/bpf_lxc.c:745-1024
  *     gf_lxc_egress_classify     <- from-container handle_ingress bpf/bpf_lxc.c:427-738
  *     gf_pipeline_classify       <- bpf_xdp -> bpf_lb -> bpf_netdev -> cilium_policy tail call
@@ -245,6 +246,48 @@ typedef struct gf_lb_out {
 /* new_daddr6 (16 B per packet, may be NULL) receives the v6 translated address. */
 int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out,
                    uint8_t *new_daddr6, void *stream);
+
+/* LB_DSTMAC (bpf_lb.c:200-205): the destination MAC written into frames the program
+ * redirects.  mac == NULL undefines it.  -EBADF: not an LB program; -EINVAL: the
+ * program was loaded without GF_LB_F_REDIRECT (LB_DSTMAC sits inside #ifdef LB_REDIRECT).
+ * The reference's eth_store_daddr(skb, mac, 0) cannot fail on a frame long enough to carry an
+ * ethertype, and its `ret = DROP_WRITE_ERROR` is overwritten by `return redirect(ifindex, 0)`
+ * anyway, so no record ever reports it.  Read by gf_lb_classify_frames only: gf_lb_classify
+ * writes no frame, and the LB stage of gf_pipeline_classify does not apply it. */
+int gf_lb_prog_set_dstmac(int prog, const uint8_t mac[6]);
+
+/* bpf_lb's from-netdev (bpf_lb.c:169-212) over raw frames: the program as bpf/init.sh:341-342
+ * attaches it to the native device of a node in lb mode, where it is the whole datapath.
+ * Dispatch on the frame's ethertype (GF_LB_F_NO_IPV4 / _NO_IPV6 and every other ethertype:
+ * TC_ACT_OK, frame untouched), handle_ipv4 / handle_ipv6 with revalidate_data (DROP_INVALID),
+ * ipv4_hdrlen / ipv6_hdrlen, extract_l4_port under GF_LB_F_L4 (DROP_UNKNOWN_L4 becomes
+ * TC_ACT_OK, frame untouched), the service lookup with its L3 fallback, lb*_select_slave with
+ * hash = flow_hash[i] (NULL: 0, as gf_pipeline_classify), lb*_lookup_slave (DROP_NO_SERVICE),
+ * lb6's new_dst.p4 |= rev_nat_index, then lb4_xlate / lb6_xlate on the frame with the quirks
+ * DESIGN.md lists for the pipeline's LB stage, and LB_DSTMAC on the frames it redirects.
+ *
+ * out[i] and new_daddr6 (16 B per packet, may be NULL) are bit for bit what gf_lb_classify
+ * returns for the same packets after gf_parse_frames, the action included: a translated frame is
+ * TC_ACT_REDIRECT with GF_LB_F_REDIRECT and TC_ACT_OK without (the record still carries the
+ * translation, and the frame is rewritten either way).
+ *
+ * snap_out: NULL = records only; frames->snap = in place (only the fields the reference writes
+ * in a translated frame are stored: dst MAC, IPv4 daddr and header checksum, IPv6 daddr, L4
+ * checksum, L4 dport; no other frame is written); any other buffer (n * snap_stride) = every
+ * frame, the untouched ones copied verbatim.  snap_stride is gf_pipeline_classify's: 14..256
+ * (-EINVAL otherwise), reads past the snap see zeros and writes past it are dropped.
+ *
+ * With an event ring set, every TC_ACT_SHOT frame appends send_drop_notify_error's record
+ * (bpf_lb.c:194-195), byte for byte the one gf_pipeline_classify appends for a frame dropped at
+ * GF_STAGE_LB (source, labels and ifindex 0, the captured bytes, the ring-full rule).  bpf_lb
+ * sends no trace notification; its cilium_dbg_capture calls (:73, :131, :206, :210) stay out, as
+ * on every other frame entry point.  The stats sink counts the call like gf_lb_classify.
+ *
+ * Errors, all before anything is launched or written: -EBADF (not an LB program), -EFAULT (NULL
+ * frames, or n > 0 with a NULL snap, len or out), -EINVAL (snap_stride), -E2BIG (n > 2^30);
+ * n == 0 returns 0. */
+int gf_lb_classify_frames(int prog, const gf_frames *frames, const uint32_t *flow_hash,
+                          gf_lb_out *out, uint8_t *new_daddr6, uint8_t *snap_out, void *stream);
 
 /* ---- endpoint ingress policy (bpf/bpf_lxc.c handle_policy) ---- */
 #define GF_LXC_F_DROP_ALL        (1u << 0)  /* DROP_ALL */
