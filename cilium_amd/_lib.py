@@ -165,6 +165,30 @@ GF_RESPOND_F_NS_TO_STACK = 1 << 0
 GF_REC_EGRESS, GF_REC_PIPELINE = 1, 2
 
 
+class gf_tunnel_cfg(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("local_ip", C.c_uint32), ("dst_port", C.c_uint16),
+                ("sport_min", C.c_uint16), ("sport_max", C.c_uint16), ("ttl", C.c_uint8), ("tos", C.c_uint8),
+                ("src_mac", C.c_uint8 * 6), ("dst_mac", C.c_uint8 * 6)]
+
+
+class gf_tunnel_tx(C.Structure):
+    _fields_ = [("frames", gf_frames), ("remote_ip", C.c_void_p), ("tunnel_id", C.c_void_p), ("opt", C.c_void_p),
+                ("opt_stride", C.c_uint32), ("opt_len", C.c_void_p), ("select", C.c_void_p),
+                ("flow_hash", C.c_void_p), ("ip_id", C.c_void_p), ("dst_mac", C.c_void_p)]
+
+
+class gf_tunnel_rx_out(C.Structure):
+    _fields_ = [("inner", C.c_void_p), ("inner_stride", C.c_uint32), ("inner_len", C.c_void_p),
+                ("tunnel_id", C.c_void_p), ("outer_saddr", C.c_void_p), ("opt", C.c_void_p),
+                ("opt_stride", C.c_uint32), ("opt_len", C.c_void_p), ("status", C.c_void_p)]
+
+
+GF_TUN_VXLAN, GF_TUN_GENEVE = 0, 1
+GF_TUN_F_UDP_CSUM, GF_TUN_F_DF = 1 << 0, 1 << 1
+(GF_TUN_ST_OK, GF_TUN_ST_SKIPPED, GF_TUN_ST_SHORT, GF_TUN_ST_BAD_OPT, GF_TUN_ST_TRUNCATED, GF_TUN_ST_NOT_TUNNEL,
+ GF_TUN_ST_BAD_OUTER, GF_TUN_ST_BAD_HDR, GF_TUN_ST_BAD_CSUM, GF_TUN_ST_OK_UNVERIFIED) = range(10)
+
+
 class gf_event_ring(C.Structure):
     _fields_ = [("records", C.c_void_p), ("capacity", C.c_uint32), ("count", C.c_void_p)]
 
@@ -221,6 +245,10 @@ _sig("gf_host_classify", C.c_int, C.c_int, C.POINTER(gf_host_batch), C.c_uint32,
 _sig("gf_respond_load", C.c_int, C.POINTER(gf_respond_cfg))
 _sig("gf_respond", C.c_int, C.c_int, C.POINTER(gf_respond_batch), VP, VP, VP)
 _sig("gf_respond_calls", C.c_int, C.POINTER(gf_frames), VP, C.c_uint32, VP, VP)
+_sig("gf_tunnel_load", C.c_int, C.POINTER(gf_tunnel_cfg))
+_sig("gf_tunnel_encap", C.c_int, C.c_int, C.POINTER(gf_tunnel_tx), VP, C.c_uint32, VP, VP, VP)
+_sig("gf_tunnel_select", C.c_int, VP, C.c_uint32, C.c_uint32, VP, VP)
+_sig("gf_tunnel_decap", C.c_int, C.c_int, C.POINTER(gf_frames), C.POINTER(gf_tunnel_rx_out), VP)
 _sig("gf_ct_gc", C.c_int, C.c_int, C.c_uint32, VP)
 _sig("gf_ct_gc_maps", C.c_int, C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), VP)
 _sig("gf_proxy_gc", C.c_int, C.c_int, C.c_uint32, VP)
@@ -255,7 +283,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lb_prog_set_dstmac", "gf_lb_classify_frames", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_tunnel_load", "gf_tunnel_encap", "gf_tunnel_select", "gf_tunnel_decap", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

@@ -102,7 +102,7 @@ struct HTab {
     void rehash(uint64_t new_nslots);
 };
 
-enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond };
+enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond, ProgTunnel };
 
 struct Obj {
     ObjKind kind;
@@ -277,6 +277,11 @@ struct ProgRespond : Obj {         // the ARP / ICMPv6 responder tail calls (gf_
     std::mutex mu;             // one gf_respond call at a time per handle (its device table)
     OrderPt ord;
     ProgRespond() : Obj(ObjKind::ProgRespond) {}
+};
+
+struct ProgTunnel : Obj {          // VXLAN / Geneve on the wire (gf_tunnel.h)
+    gf_tunnel_cfg cfg{};
+    ProgTunnel() : Obj(ObjKind::ProgTunnel) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host

@@ -9310,3 +9310,6 @@ extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t
 
 // ---- the ARP / ICMPv6 responder tail calls: k_respond, gf_respond ----
 #include "gf_respond.h"
+
+// ---- VXLAN / Geneve on the wire: k_tun_encap, k_tun_decap, gf_tunnel_* ----
+#include "gf_tunnel.h"

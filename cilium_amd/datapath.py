@@ -19,6 +19,7 @@ from .maps import ctmap
 from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
                    gf_overlay_batch, gf_tunnel_opts, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
+                   gf_tunnel_cfg, gf_tunnel_tx, gf_tunnel_rx_out, GF_TUN_GENEVE,
                    GF_CALL_ICMP6_TIME_EXCEEDED, GF_REC_EGRESS, GF_REC_PIPELINE)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
@@ -148,6 +149,7 @@ class Datapath:
         self.sc = sc
         self.fd = {}
         self._resp = {}
+        self._tun = {}
         for name, m in sc.maps.items():
             fd = bpf.CreateMap(m.type, m.ksz, m.vsz, m.max_entries, m.flags)
             if m.n():
@@ -438,6 +440,64 @@ class Datapath:
                                   flags=flags, max_len=max_len)
         return call, out, reply
 
+    # ---- VXLAN / Geneve on the wire (the kernel's tunnel device in the reference) ----
+    def tunnel_load(self, mode, dst_port, local_ip=0, flags=0, sport_min=32768, sport_max=61000, ttl=64, tos=0,
+                    src_mac=bytes(6), dst_mac=bytes(6)):
+        """gf_tunnel_load: a tunnel endpoint handle (closed with the datapath).  Addresses as
+        gf_egress_out.tunnel_ip (10.0.0.1 = 0x0a000001); dst_port has no default."""
+        cfg = gf_tunnel_cfg(mode, flags, local_ip & 0xFFFFFFFF, dst_port, sport_min, sport_max, ttl, tos,
+                            (C.c_uint8 * 6)(*src_mac), (C.c_uint8 * 6)(*dst_mac))
+        h = _check(lib.gf_tunnel_load(C.byref(cfg)), "gf_tunnel_load")
+        self._tun[h] = mode
+        return h
+
+    def tunnel_select(self, kind, records):
+        """gf_tunnel_select: the select column of tunnel_encap from a classify call's records
+        (kind GF_REC_EGRESS: GF_EG_F_ENCAP; GF_REC_PIPELINE: the redirect to ENCAP_IFINDEX)."""
+        torch = _torch()
+        n = records.shape[0]
+        sel = torch.empty(n, dtype=torch.uint8, device=records.device)
+        _check(lib.gf_tunnel_select(_ptr(records), kind, n, _ptr(sel), _stream()), "gf_tunnel_select")
+        return sel
+
+    def tunnel_encap(self, tun, frames, len, remote_ip, tunnel_id, out_stride, opt=None, opt_len=None, select=None,
+                     flow_hash=None, ip_id=None, dst_mac=None, out=None):
+        """gf_tunnel_encap over inner frames [n,stride] u8, len / remote_ip / tunnel_id [n] i32 and the
+        optional columns (device tensors; opt [n,opt_stride] u8, ip_id [n] i16, dst_mac [n,6] u8).
+        Returns (out [n,out_stride] u8, out_len [n] i32, status [n] u8); rows of frames that are not
+        GF_TUN_ST_OK keep what `out` held (a fresh buffer: uninitialised)."""
+        torch = _torch()
+        n = frames.shape[0]
+        if out is None:
+            out = torch.empty((n, out_stride), dtype=torch.uint8, device=frames.device)
+        out_len = torch.empty(n, dtype=torch.int32, device=frames.device)
+        status = torch.empty(n, dtype=torch.uint8, device=frames.device)
+        tx = gf_tunnel_tx(gf_frames(n, frames.shape[1], _ptr(frames), _ptr(len)), _ptr(remote_ip), _ptr(tunnel_id),
+                          _ptr(opt), opt.shape[1] if opt is not None else 0, _ptr(opt_len), _ptr(select),
+                          _ptr(flow_hash), _ptr(ip_id), _ptr(dst_mac))
+        _check(lib.gf_tunnel_encap(tun, C.byref(tx), _ptr(out), out_stride, _ptr(out_len), _ptr(status), _stream()),
+               "gf_tunnel_encap")
+        return out, out_len, status
+
+    def tunnel_decap(self, tun, outer, len, inner_stride=128, opt_stride=8):
+        """gf_tunnel_decap over outer frames [n,stride] u8 and len [n] i32.  Returns a namespace in
+        the layout overlay() takes: frames [n,inner_stride] u8, len, tunnel_id, outer_saddr [n] i32,
+        opt [n,opt_stride] u8 (zeros; written in Geneve mode), opt_len, status [n] u8, plus n, device,
+        tc_index and flow_hash None.  Rows and columns of frames that are not OK keep the zeros the
+        buffers start with (len is written for every frame)."""
+        import types
+        torch = _torch()
+        n, dev = outer.shape[0], outer.device
+        z = lambda dt, *shape: torch.zeros((n,) + shape, dtype=dt, device=dev)
+        r = types.SimpleNamespace(n=n, device=dev, frames=z(torch.uint8, inner_stride), len=z(torch.int32),
+                                  tunnel_id=z(torch.int32), outer_saddr=z(torch.int32), opt=z(torch.uint8, opt_stride),
+                                  opt_len=z(torch.uint8), status=z(torch.uint8), tc_index=None, flow_hash=None)
+        fr = gf_frames(n, outer.shape[1], _ptr(outer), _ptr(len))
+        ro = gf_tunnel_rx_out(_ptr(r.frames), inner_stride, _ptr(r.len), _ptr(r.tunnel_id), _ptr(r.outer_saddr),
+                              _ptr(r.opt), opt_stride, _ptr(r.opt_len), _ptr(r.status))
+        _check(lib.gf_tunnel_decap(tun, C.byref(fr), C.byref(ro), _stream()), "gf_tunnel_decap")
+        return r
+
     # ---- proxy map sweeps (pkg/maps/proxymap: GC / Flush, CleanupOnRedirectClose) ----
     def proxy_gc(self, name, filter_time):
         """gf_proxy_gc on the current stream: deletes lifetime < filter_time, returns the count."""
@@ -472,7 +532,7 @@ class Datapath:
     def close(self):
         """Close the program objects, then the maps (a program holds its maps, so
         their device tables are released once both are closed)."""
-        progs = list(self._resp.values()) + [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
+        progs = list(self._resp.values()) + list(self._tun) + [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
         for h in [h for h in progs if h] + list(self.fd.values()):
             try:
                 bpf.ObjClose(h)
@@ -481,6 +541,7 @@ class Datapath:
         self.host = self.ovl = self.pipe = self.policy_array = self.lb_prog = self.xdp_prog = None
         self.lxc_progs = []
         self._resp = {}
+        self._tun = {}
         self.fd = {}
 
 

@@ -1070,6 +1070,45 @@ def overlay_fuzz(seed=3, n_packets=20000, n_batches=3, strangers=0.1, to_host=0.
     return sc
 
 
+def tunnel_fuzz(n, mode, seed, stride=128, opt_stride=64, negatives=16):
+    """Inner frames and the transmit columns of gf_tunnel_encap (mode 0 VXLAN, 1 Geneve).  Every
+    frame can be encapsulated except `negatives` of each kind, counted in .neg: "short" (len < 14:
+    GF_TUN_ST_SHORT), "bad_opt" (Geneve: opt_len not a multiple of 4, or above the stride:
+    GF_TUN_ST_BAD_OPT), "skipped" (select 0) and "truncated" (len > stride: GF_TUN_ST_TRUNCATED with
+    the UDP checksum on, encapsulated from the snap without it).  The lengths take the edges in
+    turn: 14, 15 (odd: the checksum's tail byte), stride - 1, stride, and in between.  Geneve
+    opt_len is 0, 8, opt_stride or another multiple of 4.  Returns a namespace of numpy columns:
+    frames [n,stride] u8, lens, remote_ip, tunnel_id, flow_hash (u32), opt [n,opt_stride] u8,
+    opt_len, select (u8), ip_id (u16), dst_mac [n,6] u8."""
+    from types import SimpleNamespace
+    rng = np.random.default_rng(seed)
+    frames = rng.integers(0, 256, (n, stride), dtype=np.uint8)
+    frames[:, 12], frames[:, 13] = 0x08, 0x00
+    edges = np.array([14, 15, stride - 1, stride], np.uint32)
+    lens = np.where(rng.random(n) < 0.3, edges[rng.integers(0, 4, n)], rng.integers(14, stride + 1, n)).astype(np.uint32)
+    lens[:min(4, n)] = edges[:min(4, n)]
+    opt = rng.integers(0, 256, (n, opt_stride), dtype=np.uint8)
+    opt_len = (4 * rng.integers(0, opt_stride // 4 + 1, n)).astype(np.uint8)
+    pick = rng.random(n)
+    opt_len[pick < 0.2], opt_len[(pick >= 0.2) & (pick < 0.4)], opt_len[pick >= 0.9] = 0, min(8, opt_stride), opt_stride
+    select = np.ones(n, np.uint8)
+    k = min(negatives, n // 8)
+    idx = rng.permutation(n)[:4 * k].reshape(4, k) if k else np.zeros((4, 0), np.int64)
+    lens[idx[0]] = rng.integers(0, 14, k)
+    if mode == 1:
+        opt_len[idx[1]] = np.where(rng.random(k) < 0.5, opt_stride + 4, 4 * rng.integers(0, opt_stride // 4, k) + rng.integers(1, 4, k))
+    select[idx[2]] = 0
+    lens[idx[3]] = rng.integers(stride + 1, 1451, k)
+    return SimpleNamespace(n=n, mode=mode, stride=stride, frames=frames, lens=lens,
+                           remote_ip=(ip4("10.0.0.0") + rng.integers(1, 1 << 16, n)).astype(np.uint32),
+                           tunnel_id=rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32),
+                           flow_hash=rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32),
+                           opt=opt, opt_len=opt_len, select=select,
+                           ip_id=rng.integers(0, 1 << 16, n).astype(np.uint16),
+                           dst_mac=rng.integers(0, 256, (n, 6), dtype=np.uint8),
+                           neg={"short": k, "bad_opt": k if mode == 1 else 0, "skipped": k, "truncated": k})
+
+
 def host_fuzz(seed=3, n_packets=20000, n_batches=3, reverse=0.3, remote=0.15, encap_ifindex=7, **kw):
     """pipeline_fuzz's frames as cilium_host sees them (bpf_netdev.c with FROM_HOST): a mark
     column (a quarter each from the ingress and the egress proxy with the batch's identity

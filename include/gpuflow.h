@@ -1059,6 +1059,111 @@ int gf_overlay_classify_opts(int ovl, const gf_overlay_batch *batch, const gf_tu
 int gf_lxc_egress_tunnel_meta(int policy_array, const uint16_t *lxc_id, const gf_egress_out *records, uint32_t n,
                               uint32_t *tunnel_id, uint8_t *opt /* n*8 */, uint8_t *opt_len, void *stream);
 
+/* ---- VXLAN / Geneve on the wire: gf_tunnel_encap, gf_tunnel_decap ----
+ * The step the reference leaves to the kernel's cilium_vxlan / cilium_geneve device
+ * (bpf/init.sh:295-300, "type $MODE external"): redirect(ENCAP_IFINDEX) sends into it and
+ * from-overlay receives from it.  The reference holds no encapsulation code; it only defines the
+ * metadata (bpf/lib/encap.h:30-81).  The headers follow their RFCs: IPv4 RFC 791, UDP RFC 768,
+ * VXLAN RFC 7348 section 5, Geneve RFC 8926 section 3.4.  The underlay is IPv4 only
+ * (bpf_tunnel_key carries remote_ipv4 only).  Outer frame:
+ *   Ethernet 14 | IPv4 20 (IHL 5 on transmit) | UDP 8 | tunnel header 8 | Geneve options | inner frame
+ *   VXLAN:  08 00 00 00 | VNI(3) | 00          Geneve: opt_len/4 | 00 | 65 58 | VNI(3) | 00
+ * VNI = tunnel_id & 0xffffff.  What the kernel's device would choose itself is configuration here
+ * (INTEGRATION.md lists what an agent would pass).  Every IPv4 address of these calls (local_ip,
+ * remote_ip, outer_saddr) has the form of gf_egress_out.tunnel_ip: 10.0.0.1 is 0x0a000001, sent
+ * most significant byte first.  These are this library's rules; a Linux device differs in places
+ * (DESIGN.md). */
+#define GF_TUN_VXLAN  0
+#define GF_TUN_GENEVE 1
+#define GF_TUN_F_UDP_CSUM (1u << 0)   /* transmit: compute the outer UDP checksum (else 0) */
+#define GF_TUN_F_DF       (1u << 1)   /* transmit: set DF in the outer IPv4 header */
+typedef struct gf_tunnel_cfg {
+    uint32_t mode;          /* GF_TUN_VXLAN | GF_TUN_GENEVE */
+    uint32_t flags;         /* GF_TUN_F_* */
+    uint32_t local_ip;      /* outer saddr on transmit; on receive the daddr a tunnel packet must have (0 = any) */
+    uint16_t dst_port;      /* host order: 8472 or 4789 for VXLAN, 6081 for Geneve; never defaulted (0: -EINVAL) */
+    uint16_t sport_min, sport_max;  /* source port = sport_min + ((u64)flow_hash * (sport_max - sport_min) >> 32) */
+    uint8_t  ttl, tos;
+    uint8_t  src_mac[6], dst_mac[6];   /* outer Ethernet; dst_mac is the next hop unless the batch has a column */
+} gf_tunnel_cfg;            /* 32 B */
+/* -EFAULT (NULL), -EINVAL (mode, unknown flags, dst_port 0, sport_min > sport_max). */
+int gf_tunnel_load(const gf_tunnel_cfg *cfg);
+
+#define GF_TUN_ST_OK            0
+#define GF_TUN_ST_SKIPPED       1   /* encap: select[i] == 0 */
+#define GF_TUN_ST_SHORT         2   /* encap: len < 14 */
+#define GF_TUN_ST_BAD_OPT       3   /* encap, Geneve: opt_len not a multiple of 4, > opt_stride or > 64 */
+#define GF_TUN_ST_TRUNCATED     4   /* encap with GF_TUN_F_UDP_CSUM: len > snap_stride, the datagram cannot be summed */
+#define GF_TUN_ST_NOT_TUNNEL    5   /* decap: not addressed to this tunnel endpoint */
+#define GF_TUN_ST_BAD_OUTER     6   /* decap: malformed Ethernet / IPv4 / UDP */
+#define GF_TUN_ST_BAD_HDR       7   /* decap: malformed VXLAN / Geneve header */
+#define GF_TUN_ST_BAD_CSUM      8   /* decap: the UDP checksum was verified and is wrong */
+#define GF_TUN_ST_OK_UNVERIFIED 9   /* decap: a UDP checksum is present but the datagram is longer than the snap */
+
+typedef struct gf_tunnel_tx {
+    gf_frames frames;            /* DEVICE inner frames, snap_stride 14..256 as everywhere else */
+    const uint32_t *remote_ip;   /* DEVICE, as gf_egress_out.tunnel_ip; required */
+    const uint32_t *tunnel_id;   /* DEVICE, required */
+    const uint8_t  *opt; uint32_t opt_stride; const uint8_t *opt_len;   /* Geneve only, gf_tunnel_opts' rules; opt NULL = no options */
+    const uint8_t  *select;      /* DEVICE, may be NULL: 0 = leave this frame out */
+    const uint32_t *flow_hash;   /* DEVICE, may be NULL (source port sport_min) */
+    const uint16_t *ip_id;       /* DEVICE, may be NULL (identification 0) */
+    const uint8_t  *dst_mac;     /* DEVICE n*6, may be NULL (gf_tunnel_cfg.dst_mac) */
+} gf_tunnel_tx;                  /* 96 B */
+/* Per frame, first match: SKIPPED, SHORT, BAD_OPT, TRUNCATED, else OK.  For an OK frame
+ * out_len[i] = len + 50 (+ opt_len in Geneve mode), the outer total length and UDP length come from
+ * the true len, and row i of out (out_stride bytes per frame) holds the outer headers followed by
+ * the first min(len, snap_stride) inner bytes, cut at out_stride; no byte of the row past those is
+ * written.  The IPv4 header checksum is always set.  The UDP checksum is 0 without
+ * GF_TUN_F_UDP_CSUM; with it, it covers the pseudo-header and the whole datagram, a computed 0 is
+ * sent as 0xffff, and a frame with len > snap_stride is TRUNCATED.  Every other status: out_len[i]
+ * = 0 and the row untouched.  len + 36 + opt_len must fit the 16-bit total length (no GSO, no
+ * fragmentation).  A VXLAN-mode handle ignores the option columns.
+ * -EBADF; -EFAULT (a NULL batch, frame pointer, remote_ip, tunnel_id, out, out_len or status, or
+ * opt without opt_len); -EINVAL (snap_stride outside 14..256; out_stride not a multiple of 16,
+ * < 128 or > 512; out not 16-byte aligned or == frames.snap; Geneve opt_stride outside 4..64, not a
+ * multiple of 4, or opt not 4-byte aligned); -E2BIG; n == 0 returns 0.  Every refusal precedes any
+ * launch. */
+int gf_tunnel_encap(int tun, const gf_tunnel_tx *b, uint8_t *out, uint32_t out_stride,
+                    uint32_t *out_len, uint8_t *status, void *stream);
+/* The select column of gf_tunnel_encap from the records of a classify call (rec_kind as
+ * gf_respond_calls): GF_REC_EGRESS: eg_flags & GF_EG_F_ENCAP; GF_REC_PIPELINE: action REDIRECT and
+ * ifindex_lo == gf_node_cfg.encap_ifindex != 0 (gf_pipeline_classify_tunnel, gf_host_classify).
+ * -EINVAL (rec_kind), -EFAULT, -E2BIG; n == 0 returns 0. */
+int gf_tunnel_select(const void *records, uint32_t rec_kind, uint32_t n, uint8_t *select, void *stream);
+
+typedef struct gf_tunnel_rx_out {
+    uint8_t  *inner; uint32_t inner_stride;  /* 14..256 */
+    uint32_t *inner_len, *tunnel_id, *outer_saddr;
+    uint8_t  *opt; uint32_t opt_stride; uint8_t *opt_len;    /* gf_tunnel_opts' layout; may be NULL in VXLAN mode */
+    uint8_t  *status;
+} gf_tunnel_rx_out;              /* 72 B */
+/* outer: DEVICE frames as received from the wire, snap_stride 64..512.  The output columns have
+ * the layout gf_overlay_batch and gf_tunnel_opts take, so they go to gf_overlay_classify_opts
+ * without a copy.  cap = min(len, snap_stride).  Status per frame, first match:
+ *   cap < 14                                                             BAD_OUTER
+ *   ethertype != 0x0800                                                  NOT_TUNNEL
+ *   cap < 34                                                             BAD_OUTER
+ *   protocol != 17, MF set or fragment offset != 0, or daddr != local_ip (when set)  NOT_TUNNEL
+ *   version != 4 or IHL < 5; the UDP header not inside cap               BAD_OUTER
+ *   destination port != dst_port                                         NOT_TUNNEL
+ *   IPv4 total length != len - 14 or UDP length != len - 14 - 4 IHL; the tunnel header not
+ *     inside cap; the IPv4 header checksum wrong (IHL > 5 is accepted and skipped)  BAD_OUTER
+ *   VXLAN: flags byte != 0x08 or a reserved byte != 0.  Geneve: version != 0, protocol != 0x6558,
+ *     the C bit set, or the options run past the datagram or the snap    BAD_HDR
+ *   UDP checksum != 0 and len <= snap_stride: wrong sum BAD_CSUM; len > snap_stride OK_UNVERIFIED
+ *   else OK.
+ * OK and OK_UNVERIFIED: inner_len = len - headers, row i of inner holds the first
+ * min(inner_len, cap - headers, inner_stride) inner bytes (nothing past them is written),
+ * tunnel_id = VNI, outer_saddr, opt_len = the option bytes present (0 in VXLAN mode) and, in
+ * Geneve mode, the first min(opt_len, opt_stride) option bytes in row i of opt.  Every other status:
+ * inner_len = 0 and nothing else written.
+ * -EBADF; -EFAULT (NULL outer, out, a frame pointer, inner, inner_len, tunnel_id, outer_saddr or
+ * status; opt or opt_len in Geneve mode); -EINVAL (snap_stride outside 64..512, inner_stride
+ * outside 14..256, Geneve opt_stride outside 4..64 or not a multiple of 4, opt not 4-byte aligned,
+ * inner == outer->snap); -E2BIG; n == 0 returns 0. */
+int gf_tunnel_decap(int tun, const gf_frames *outer, const gf_tunnel_rx_out *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
