@@ -196,6 +196,23 @@ class gf_event_ring(C.Structure):
 GF_EVENT_RECORD = 160
 
 
+class gf_event_filter_cfg(C.Structure):
+    _fields_ = [("type_mask", C.c_uint32), ("frm", C.POINTER(C.c_uint16)), ("n_from", C.c_uint32),
+                ("to", C.POINTER(C.c_uint16)), ("n_to", C.c_uint32), ("related", C.POINTER(C.c_uint16)),
+                ("n_related", C.c_uint32)]
+
+
+class gf_event_drain_out(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("lost", C.c_uint32), ("seen", C.c_uint32), ("matched", C.c_uint32),
+                ("written", C.c_uint32), ("unknown", C.c_uint32), ("bytes", C.c_uint64), ("by_type", C.c_uint32 * 5),
+                ("pad", C.c_uint32)]
+
+
+GF_EVF_MAX_IDS = 65536
+GF_EVD_F_PACKED, GF_EVD_F_RESET = 1 << 0, 1 << 1
+GF_EVD_MAX_WINDOW = 1 << 24
+
+
 def _sig(name, res, *args):
     f = getattr(lib, name)
     f.restype = res
@@ -249,6 +266,9 @@ _sig("gf_tunnel_load", C.c_int, C.POINTER(gf_tunnel_cfg))
 _sig("gf_tunnel_encap", C.c_int, C.c_int, C.POINTER(gf_tunnel_tx), VP, C.c_uint32, VP, VP, VP)
 _sig("gf_tunnel_select", C.c_int, VP, C.c_uint32, C.c_uint32, VP, VP)
 _sig("gf_tunnel_decap", C.c_int, C.c_int, C.POINTER(gf_frames), C.POINTER(gf_tunnel_rx_out), VP)
+_sig("gf_event_filter_load", C.c_int, C.POINTER(gf_event_filter_cfg))
+_sig("gf_event_drain", C.c_int, C.c_int, C.POINTER(gf_event_ring), C.c_uint32, C.c_uint32, C.c_uint32, VP, C.c_uint64,
+     VP, VP, VP)
 _sig("gf_ct_gc", C.c_int, C.c_int, C.c_uint32, VP)
 _sig("gf_ct_gc_maps", C.c_int, C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), VP)
 _sig("gf_proxy_gc", C.c_int, C.c_int, C.c_uint32, VP)
@@ -283,7 +303,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lb_prog_set_dstmac", "gf_lb_classify_frames", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_tunnel_load", "gf_tunnel_encap", "gf_tunnel_select", "gf_tunnel_decap", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_tunnel_load", "gf_tunnel_encap", "gf_tunnel_select", "gf_tunnel_decap", "gf_event_filter_load", "gf_event_drain", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

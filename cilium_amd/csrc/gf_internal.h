@@ -102,7 +102,7 @@ struct HTab {
     void rehash(uint64_t new_nslots);
 };
 
-enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond, ProgTunnel };
+enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond, ProgTunnel, EventFilter };
 
 struct Obj {
     ObjKind kind;
@@ -282,6 +282,15 @@ struct ProgRespond : Obj {         // the ARP / ICMPv6 responder tail calls (gf_
 struct ProgTunnel : Obj {          // VXLAN / Geneve on the wire (gf_tunnel.h)
     gf_tunnel_cfg cfg{};
     ProgTunnel() : Obj(ObjKind::ProgTunnel) {}
+};
+
+struct EventFilter : Obj {         // cilium monitor's --type / --from / --to / --related-to (gf_events.h)
+    uint32_t type_mask = 0;
+    bool given[3] = {};            // from, to, related: the flag was given (n != 0)
+    std::vector<uint32_t> bits;    // three 65536-bit bitmaps, in that order
+    DevBuf d_bits;                 // their device copy, uploaded by the first drain
+    std::mutex mu;
+    EventFilter() : Obj(ObjKind::EventFilter) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host

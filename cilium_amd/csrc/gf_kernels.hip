@@ -9313,3 +9313,6 @@ extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t
 
 // ---- VXLAN / Geneve on the wire: k_tun_encap, k_tun_decap, gf_tunnel_* ----
 #include "gf_tunnel.h"
+
+// ---- draining the event ring with cilium monitor's filters: k_evd_*, gf_event_drain ----
+#include "gf_events.h"

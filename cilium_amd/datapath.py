@@ -20,6 +20,7 @@ from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
                    gf_overlay_batch, gf_tunnel_opts, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
                    gf_tunnel_cfg, gf_tunnel_tx, gf_tunnel_rx_out, GF_TUN_GENEVE,
+                   gf_event_ring, gf_event_drain_out, GF_EVENT_RECORD, GF_EVD_F_PACKED, GF_EVD_F_RESET, GF_EVD_MAX_WINDOW,
                    GF_CALL_ICMP6_TIME_EXCEEDED, GF_REC_EGRESS, GF_REC_PIPELINE)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
@@ -150,6 +151,7 @@ class Datapath:
         self.fd = {}
         self._resp = {}
         self._tun = {}
+        self.ring = None
         for name, m in sc.maps.items():
             fd = bpf.CreateMap(m.type, m.ksz, m.vsz, m.max_entries, m.flags)
             if m.n():
@@ -498,6 +500,45 @@ class Datapath:
         _check(lib.gf_tunnel_decap(tun, C.byref(fr), C.byref(ro), _stream()), "gf_tunnel_decap")
         return r
 
+    # ---- the event ring and its drain (cilium monitor's filters on the device) ----
+    def set_event_ring(self, capacity, device="cuda"):
+        """gf_set_event_ring over a fresh ring of `capacity` slots (None: no ring).  The ring is
+        the library's, not this object's: close() unsets it."""
+        torch = _torch()
+        if capacity is None:
+            _check(lib.gf_set_event_ring(None), "gf_set_event_ring")
+            self.ring = None
+            return None
+        recs = torch.zeros((max(capacity, 1), GF_EVENT_RECORD), dtype=torch.uint8, device=device)
+        cnt = torch.zeros(1, dtype=torch.int32, device=device)
+        self.ring = (recs, cnt, gf_event_ring(recs.data_ptr(), capacity, cnt.data_ptr()))
+        _check(lib.gf_set_event_ring(C.byref(self.ring[2])), "gf_set_event_ring")
+        return self.ring
+
+    def event_drain(self, filter, first=0, max_n=0, packed=False, reset=False, out_records=None):
+        """gf_event_drain over the ring of set_event_ring with a monitor.EventFilter, on the
+        current stream.  out_records: a uint8 device tensor to store into (default: room for every
+        record of the window).  Returns (out, offsets, res): the output tensor, the [window + 1]
+        int32 offsets tensor and the gf_event_drain_out fields as a dict (read after a stream
+        synchronise; res["written"] records, res["bytes"] bytes of `out` and res["written"] + 1
+        offsets are defined)."""
+        torch = _torch()
+        recs, cnt, ring = self.ring
+        window = min(max_n or GF_EVD_MAX_WINDOW, ring.capacity)
+        if out_records is None:
+            out_records = torch.empty((max(min(window, max(ring.capacity - first, 0)), 1), GF_EVENT_RECORD),
+                                      dtype=torch.uint8, device=recs.device)
+        off = torch.empty(window + 1, dtype=torch.int32, device=recs.device)
+        res = torch.zeros(C.sizeof(gf_event_drain_out), dtype=torch.uint8, device=recs.device)
+        flags = (GF_EVD_F_PACKED if packed else 0) | (GF_EVD_F_RESET if reset else 0)
+        _check(lib.gf_event_drain(filter.handle, C.byref(ring), first, max_n, flags, _ptr(out_records),
+                                  out_records.numel(), _ptr(off), _ptr(res), _stream()), "gf_event_drain")
+        torch.cuda.current_stream().synchronize()
+        r = gf_event_drain_out.from_buffer_copy(res.cpu().numpy().tobytes())
+        d = {k: getattr(r, k) for k, _ in gf_event_drain_out._fields_ if k != "pad"}
+        d["by_type"] = list(r.by_type)
+        return out_records, off, d
+
     # ---- proxy map sweeps (pkg/maps/proxymap: GC / Flush, CleanupOnRedirectClose) ----
     def proxy_gc(self, name, filter_time):
         """gf_proxy_gc on the current stream: deletes lifetime < filter_time, returns the count."""
@@ -543,6 +584,8 @@ class Datapath:
         self._resp = {}
         self._tun = {}
         self.fd = {}
+        if getattr(self, "ring", None) is not None:
+            self.set_event_ring(None)
 
 
 def to_numpy(t, dtype):

@@ -98,3 +98,78 @@ def decode_ring(records, count=None):
     a = np.asarray(records, np.uint8).reshape(-1, EVENT_RECORD)
     n = len(a) if count is None else min(int(count), len(a))
     return [decode(a[k]) for k in range(n)]
+
+
+# ---- cilium monitor's filters (cilium/cmd/monitor.go:108-156) ----
+def endpoints(rec):
+    """(type, source, destination) as the four handlers of cilium/cmd/monitor.go pass them to
+    match (:165,182,199,215): the destination is uint16(DstID) of a drop record, DstID of a trace
+    record and 0 of a debug message or capture.  `rec` is a slot (bytes, uint8 array) or a dict of
+    decode()."""
+    if isinstance(rec, dict):
+        t, src = rec["type"], rec["source"]
+        dst = rec.get("dst_id", 0) & 0xffff if t in (NOTIFY_DROP, NOTIFY_TRACE) else 0
+        return t, src, dst
+    b = bytes(rec[:28])
+    t, _sub, src = struct.unpack_from("<BBH", b, 0)
+    dst = struct.unpack_from("<H", b, 24)[0] if t in (NOTIFY_DROP, NOTIFY_TRACE) else 0
+    return t, src, dst
+
+
+def match(rec, types=(), frm=(), to=(), related=()):
+    """match() of cilium/cmd/monitor.go:144-156 over one record: an empty list is a flag that
+    was not given.  A record of a type other than 1..4 never matches (the reference prints
+    "Unknown event" for it whatever the filter)."""
+    t, src, dst = endpoints(rec)
+    if not NOTIFY_DROP <= t <= NOTIFY_TRACE:
+        return False
+    if len(types) and t not in types:
+        return False
+    if len(frm) and src not in frm:
+        return False
+    if len(to) and dst not in to:
+        return False
+    if len(related) and src not in related and dst not in related:
+        return False
+    return True
+
+
+class EventFilter:
+    """A gf_event_filter_load handle: `cilium monitor --type --from --to --related-to` for
+    gf_event_drain (Datapath.event_drain).  types: message types 1..4; frm / to / related:
+    endpoint ids (u16)."""
+
+    def __init__(self, types=(), frm=(), to=(), related=()):
+        import ctypes as C
+        from ._lib import lib, gf_event_filter_cfg
+        self.types, self.frm, self.to, self.related = tuple(types), tuple(frm), tuple(to), tuple(related)
+        mask = 0
+        for t in self.types:
+            mask |= 1 << t
+        lists = [(C.c_uint16 * max(len(x), 1))(*x) for x in (self.frm, self.to, self.related)]
+        cfg = gf_event_filter_cfg(mask, lists[0], len(self.frm), lists[1], len(self.to), lists[2], len(self.related))
+        self._lib = lib
+        self.handle = lib.gf_event_filter_load(C.byref(cfg))
+        if self.handle < 0:
+            raise OSError(-self.handle, "gf_event_filter_load")
+
+    def match(self, rec):
+        return match(rec, self.types, self.frm, self.to, self.related)
+
+    def close(self):
+        if self.handle > 0:
+            self._lib.gf_obj_close(self.handle)
+            self.handle = 0
+
+
+def decode_packed(buf, offsets):
+    """The records of a packed drain (GF_EVD_F_PACKED) as dicts: `offsets` holds the byte offset
+    of every record and the total, as gf_event_drain's out_off does."""
+    a = np.asarray(buf, np.uint8).reshape(-1)
+    off = [int(x) for x in offsets]
+    out = []
+    for lo, hi in zip(off[:-1], off[1:]):
+        slot = np.zeros(EVENT_RECORD, np.uint8)
+        slot[:hi - lo] = a[lo:hi]
+        out.append(decode(slot))
+    return out

@@ -1164,6 +1164,68 @@ typedef struct gf_tunnel_rx_out {
  * inner == outer->snap); -E2BIG; n == 0 returns 0. */
 int gf_tunnel_decap(int tun, const gf_frames *outer, const gf_tunnel_rx_out *out, void *stream);
 
+/* ---- draining the event ring on the device: gf_event_filter_load, gf_event_drain ----
+ * The consumer's half of the monitor path: `cilium monitor --type --from --to --related-to`
+ * (cilium/cmd/monitor.go:108-156) applied to a ring of GF_EVENT_RECORD slots before anything
+ * crosses PCIe.  match() (monitor.go:144-156) gets, per record (monitor.go:165,182,199,215):
+ *   type   byte 0 (1 drop, 2 debug, 3 capture, 4 trace: pkg/monitor/types.go:29-33)
+ *   src    the u16 at byte 2 (Source of all four layouts)
+ *   dst    drop: uint16(dn.DstID), the low 16 bits of the u32 at byte 24 (0x10005 matches --to 5);
+ *          trace: the u16 at byte 24; debug and capture: 0
+ * and passes the record when, in this order: type_mask is 0 or has bit `type`; from is not given
+ * or holds src; to is not given or holds dst; related is not given or holds src or dst.  A record
+ * whose type is not 1..4 ("Unknown event" in the reference, whatever the filter) never passes and
+ * is counted in `unknown`. */
+#define GF_EVF_MAX_IDS 65536u
+typedef struct gf_event_filter_cfg {
+    uint32_t type_mask;        /* bit t set = message type t passes; 0 = no --type given, every type passes */
+    const uint16_t *from;  uint32_t n_from;      /* HOST lists; n == 0 = flag not given */
+    const uint16_t *to;    uint32_t n_to;
+    const uint16_t *related; uint32_t n_related;
+} gf_event_filter_cfg;         /* 56 B */
+/* A filter handle (gf_obj_close frees it); the lists are copied.  On the device the filter is three
+ * 65536-bit bitmaps, built here and uploaded by the handle's first gf_event_drain (the one call that
+ * waits for a copy).  -EFAULT (NULL cfg, a NULL list with n != 0), -EINVAL (a type_mask bit outside
+ * 1..4), -E2BIG (a list longer than GF_EVF_MAX_IDS). */
+int gf_event_filter_load(const gf_event_filter_cfg *cfg);
+
+#define GF_EVD_F_PACKED (1u << 0)   /* wire-length records instead of 160-B slots */
+#define GF_EVD_F_RESET  (1u << 1)   /* set *ring->count = 0 once the drain has read it */
+#define GF_EVD_MAX_WINDOW (1u << 24)
+typedef struct gf_event_drain_out {  /* DEVICE, written by the call */
+    uint32_t count;        /* *ring->count as the call found it */
+    uint32_t lost;         /* max(count, capacity) - capacity: the ring's overrun */
+    uint32_t seen;         /* records examined: those of [first, min(count, capacity, first + max_n)) */
+    uint32_t matched;      /* of those, records that pass the filter */
+    uint32_t written;      /* of those, records stored in out (a prefix, in ring order) */
+    uint32_t unknown;      /* records whose type is not 1..4: never matched */
+    uint64_t bytes;        /* bytes stored in out */
+    uint32_t by_type[5];   /* matched records per type (index 0 unused) */
+    uint32_t pad;
+} gf_event_drain_out;      /* 56 B */
+/* Examines the records [first, min(*ring->count, capacity, first + max_n)) of `ring` (max_n == 0:
+ * to the end, at most GF_EVD_MAX_WINDOW records) and stores those that pass `filter` in `out`, in
+ * ring order.  Without GF_EVD_F_PACKED each stored record is its whole 160-byte slot and written =
+ * min(matched, out_bytes / 160).  With it a record takes its wire length (drop and trace 32 +
+ * len_cap, debug message 20, capture 24 + len_cap; len_cap is the u32 at byte 12; the result
+ * clamped to 160) rounded up to a multiple of 8 with zero bytes, and records are stored while the
+ * running total fits out_bytes: the first one that does not fit ends the output.  out_off (may be
+ * NULL; room for min(max_n ? max_n : GF_EVD_MAX_WINDOW, capacity) + 1 u32) receives the byte offset
+ * of every stored record and the total at index `written`.  No byte of out past res->bytes and no
+ * word of out_off past index `written` is written.  res is always written; first >= min(count,
+ * capacity) gives seen = 0.  out_bytes == 0 (out may then be NULL) only counts.
+ * The call is stream-ordered like the classify calls that fill the ring (with the ring of
+ * gf_set_event_ring it also takes its turn among calls on other streams): it reads *ring->count on
+ * the device and waits for nothing on the host; with GF_EVD_F_RESET the ring is empty for the next
+ * classify call on that stream.  Three launches (k_evd_count, k_evd_scan, k_evd_scatter); no block
+ * waits for another.  16-byte copies when records and out are 16-byte aligned (slot mode), 8-byte
+ * copies when both are 8-byte aligned (packed mode), byte copies otherwise.
+ * Every refusal precedes any launch and writes nothing: -EBADF (filter); -EFAULT (NULL ring,
+ * ring->records, ring->count or res; NULL out with out_bytes != 0); -EINVAL (an unknown flag, out
+ * overlapping the ring's records, records not 4-byte aligned); -E2BIG (max_n > GF_EVD_MAX_WINDOW). */
+int gf_event_drain(int filter, const gf_event_ring *ring, uint32_t first, uint32_t max_n, uint32_t flags,
+                   uint8_t *out, uint64_t out_bytes, uint32_t *out_off, gf_event_drain_out *res, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
