@@ -63,6 +63,11 @@ class gf_xdp_cfg(C.Structure):
                 ("cidr6_lmap", C.c_int), ("lxc_map", C.c_int)]
 
 
+class gf_xdp_frames_out(C.Structure):
+    _fields_ = [("verdict", C.c_void_p), ("snap", C.c_void_p), ("len", C.c_void_p), ("index", C.c_void_p),
+                ("max_out", C.c_uint32), ("counts", C.c_void_p)]
+
+
 class gf_lb_cfg(C.Structure):
     _fields_ = [("lb4_services", C.c_int), ("lb6_services", C.c_int), ("flags", C.c_uint32),
                 ("redirect_ifindex", C.c_uint32)]
@@ -238,6 +243,7 @@ _sig("gf_now_sec", C.c_uint32)
 _sig("gf_parse_frames", C.c_int, C.POINTER(gf_frames), C.POINTER(gf_pkt_cols_out), VP)
 _sig("gf_xdp_prog_load", C.c_int, C.POINTER(gf_xdp_cfg))
 _sig("gf_xdp_classify", C.c_int, C.c_int, C.POINTER(gf_pkt_cols), VP, VP)
+_sig("gf_xdp_filter_frames", C.c_int, C.c_int, C.POINTER(gf_frames), C.POINTER(gf_xdp_frames_out), VP)
 _sig("gf_lb_prog_load", C.c_int, C.POINTER(gf_lb_cfg))
 _sig("gf_lb_classify", C.c_int, C.c_int, C.POINTER(gf_pkt_cols), VP, VP, VP)
 _sig("gf_lb_prog_set_dstmac", C.c_int, C.c_int, VP)
@@ -301,7 +307,7 @@ EXPORTED = [
     "gf_map_create", "gf_map_update_elem", "gf_map_lookup_elem", "gf_map_delete_elem",
     "gf_map_get_next_key", "gf_map_update_batch", "gf_map_lookup_batch", "gf_map_get_info", "gf_obj_pin", "gf_obj_get",
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
-    "gf_xdp_classify", "gf_lb_prog_load", "gf_lb_classify", "gf_lb_prog_set_dstmac", "gf_lb_classify_frames", "gf_lxc_prog_load",
+    "gf_xdp_classify", "gf_xdp_filter_frames", "gf_lb_prog_load", "gf_lb_classify", "gf_lb_prog_set_dstmac", "gf_lb_classify_frames", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
     "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_tunnel_load", "gf_tunnel_encap", "gf_tunnel_select", "gf_tunnel_decap", "gf_event_filter_load", "gf_event_drain", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",

@@ -216,6 +216,8 @@ struct Map : Obj {
 struct ProgXdp : Obj {
     gf_xdp_cfg cfg{};
     std::shared_ptr<Map> m4h, m4l, m6h, m6l, lxc;
+    DevBuf ff_ws;              // gf_xdp_filter_frames: the tiles' pass counts, then the verdict bytes when the caller takes none
+    std::mutex ff_mu;          // one gf_xdp_filter_frames call at a time per handle (its workspace)
     ProgXdp() : Obj(ObjKind::ProgXdp) {}
 };
 struct ProgLb : Obj {

@@ -307,6 +307,34 @@ struct PktHdrA {
     __device__ __forceinline__ uint4 saddr6() const { return make_uint4(h.s6[0], h.s6[1], h.s6[2], h.s6[3]); }
     __device__ __forceinline__ uint4 daddr6() const { return make_uint4(h.d6[0], h.d6[1], h.d6[2], h.d6[3]); }
 };
+// The prefilter's three fields straight from a frame's row (k_xdpf_verdict): ethertype and
+// the addresses under parse_row's rules, loaded when xdp_verdict asks for them; nothing else
+// of PktHdr.  cap = min(len, snap_stride): a byte at or past it reads 0.  w4 / w6: the rows are
+// 4-byte aligned and hold bytes [0, 36) / [0, 56), so the IPv4 / IPv6 addresses (all at offsets
+// == 2 mod 4) come from whole dwords; xdp_verdict reads them only when len >= 34 / 54, and then
+// every byte used lies below cap.
+struct FrameA {
+    const uint8_t *f;
+    uint32_t cap;
+    bool w4, w6;
+    __device__ __forceinline__ uint32_t dw(uint32_t off) const { return *reinterpret_cast<const uint32_t *>(f + off); }
+    __device__ __forceinline__ uint32_t mid(uint32_t off) const { return (dw(off - 2) >> 16) | (dw(off + 2) << 16); }
+    __device__ __forceinline__ uint32_t b4(uint32_t off) const {
+        return fbyte(f, cap, off) | (fbyte(f, cap, off + 1) << 8) | (fbyte(f, cap, off + 2) << 16) | (fbyte(f, cap, off + 3) << 24);
+    }
+    __device__ __forceinline__ uint32_t et(uint32_t len) const {
+        return len >= 14 ? ((fbyte(f, cap, 12) << 8) | fbyte(f, cap, 13)) : 0u;
+    }
+    __device__ __forceinline__ uint32_t saddr4() const { return w4 ? mid(26) : b4(26); }
+    __device__ __forceinline__ uint32_t daddr4() const { return w4 ? mid(30) : b4(30); }
+    __device__ __forceinline__ bool has6() const { return true; }
+    __device__ __forceinline__ uint4 saddr6() const {
+        return w6 ? make_uint4(mid(22), mid(26), mid(30), mid(34)) : make_uint4(b4(22), b4(26), b4(30), b4(34));
+    }
+    __device__ __forceinline__ uint4 daddr6() const {
+        return w6 ? make_uint4(mid(38), mid(42), mid(46), mid(50)) : make_uint4(b4(38), b4(42), b4(46), b4(50));
+    }
+};
 
 // The lane's frame copy.  Reads past the snap (or len) are 0, writes past the
 // snap are dropped (the snap holds every header byte the programs touch).
@@ -9316,3 +9344,6 @@ extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t
 
 // ---- draining the event ring with cilium monitor's filters: k_evd_*, gf_event_drain ----
 #include "gf_events.h"
+
+// ---- the prefilter over raw frames: k_xdpf_*, gf_xdp_filter_frames ----
+#include "gf_xdp_frames.h"

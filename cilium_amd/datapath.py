@@ -16,7 +16,7 @@ import numpy as np
 
 from . import bpf
 from .maps import ctmap
-from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_lb_cfg, gf_lxc_cfg,
+from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_xdp_frames_out, gf_lb_cfg, gf_lxc_cfg,
                    gf_node_cfg, gf_netdev_cfg, gf_pipeline_cfg, gf_pipe_batch, gf_lxc_batch, gf_overlay_cfg,
                    gf_overlay_batch, gf_tunnel_opts, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
                    gf_tunnel_cfg, gf_tunnel_tx, gf_tunnel_rx_out, GF_TUN_GENEVE,
@@ -238,6 +238,27 @@ class Datapath:
         c = b.cols()
         _check(lib.gf_xdp_classify(self.xdp_prog, C.byref(c), _ptr(out), _stream()), "gf_xdp_classify")
         return out
+
+    def xdp_filter_frames(self, b, max_out=None, frames=True, verdict=True, index=True):
+        """gf_xdp_filter_frames: the prefilter over the batch's frames.  Returns (verdict [n] u8,
+        frames [max_out,stride] u8, len [max_out] i32, index [max_out] i32, counts [4] i32 =
+        passed, dropped, written, 0), all on the device; the first counts[2] rows of frames, len
+        and index are the XDP_PASS frames in batch order.  max_out: their capacity (default b.n).
+        frames=False: verdict and counts only (frames, len and index are None); verdict=False /
+        index=False: that output is not taken (None)."""
+        torch = _torch()
+        cap = b.n if max_out is None else max_out
+        stride = b.frames.shape[1] if b.n else 64
+        e = lambda dt, *shape: torch.empty(shape, dtype=dt, device=b.device)
+        v = e(torch.uint8, b.n) if verdict else None
+        snap = e(torch.uint8, cap, stride) if frames else None
+        ln = e(torch.int32, cap) if frames else None
+        ix = e(torch.int32, cap) if frames and index else None
+        counts = e(torch.int32, 4)
+        fr = gf_frames(b.n, stride, _ptr(b.frames), _ptr(b.len))
+        o = gf_xdp_frames_out(_ptr(v), _ptr(snap), _ptr(ln), _ptr(ix), cap, _ptr(counts))
+        _check(lib.gf_xdp_filter_frames(self.xdp_prog, C.byref(fr), C.byref(o), _stream()), "gf_xdp_filter_frames")
+        return v, snap, ln, ix, counts
 
     def lb(self, b):
         torch = _torch()

@@ -29,6 +29,7 @@
  *     bpf/lxc_config.h, bpf/netdev_config.h); a classify call runs the
  *     program over one batch of packets that is resident in HBM.
  *     gf_xdp_classify            <- xdp_start/check_filters   bpf/bpf_xdp.c:88-184
+ *     gf_xdp_filter_frames       <- the same over raw frames: the XDP_PASS frames packed in arrival order
  *     gf_lb_classify             <- from_netdev (bpf_lb)      bpf/bpf_lb.c:58-212
  *     gf_lb_classify_frames      <- the same over raw frames, with lb*_xlate's rewrites and LB_DSTMAC
  *     gf_policy_ingress_classify <- handle_policy/ipv{4,6}_policy bpf/bpf_lxc.c:745-1024
@@ -220,6 +221,43 @@ typedef struct gf_xdp_cfg {
 int gf_xdp_prog_load(const gf_xdp_cfg *cfg);
 /* verdict[i] = GF_XDP_DROP / GF_XDP_PASS. */
 int gf_xdp_classify(int prog, const gf_pkt_cols *pkts, uint8_t *verdict, void *stream);
+
+/* bpf_xdp.o as bpf/init.sh attaches it to --prefilter-device (bpf/bpf_xdp.c:158-184), over raw
+ * frames: the one program that removes traffic.  Frames in, fewer frames out, in arrival order,
+ * as the gf_frames every later frame entry point takes (gf_lb_classify_frames,
+ * gf_pipeline_classify, gf_tunnel_decap).
+ *
+ * verdict[i] is bit for bit what gf_xdp_classify returns for the same frames after
+ * gf_parse_frames with the IPv6 columns present: len < 14 drops, IPv4 with len < 34 and IPv6 with
+ * len < 54 drop, every other ethertype passes, reads past min(len, snap_stride) see zeros.
+ *
+ * The j-th row of out->snap is the whole row (snap_stride bytes, verbatim, the bytes past len
+ * included) of the j-th XDP_PASS frame in batch order; len[j] is its wire length and index[j] its
+ * batch index i, the handle for any side column (flow_hash, tc_index) the caller carries along.
+ * The order is stable.  When more than max_out frames pass, the first max_out are written and
+ * counts reports both figures: the call is asynchronous and cannot fail late.  Nothing at or past
+ * row counts[2] is written in snap, len or index.  There is no in-place mode.
+ *
+ * The call takes the locks of the program's maps and sees their state at the batch boundary, as
+ * gf_xdp_classify does, and the stats sink counts it exactly as gf_xdp_classify would for these
+ * frames.  bpf_xdp sends no events: the event ring is not touched.
+ *
+ * Errors, all before anything is launched or written: -EBADF (not an XDP program), -EFAULT (NULL
+ * frames, out or counts; n > 0 with a NULL frames->snap or frames->len; out->snap without
+ * out->len), -EINVAL (n > 0 with snap_stride outside 14..256; out->snap NULL with out->len or
+ * out->index; an output buffer that overlaps frames->snap or frames->len), -E2BIG (n > 2^30).
+ * n == 0 returns 0 and writes only counts (zeros). */
+typedef struct gf_xdp_frames_out {
+    uint8_t  *verdict;   /* DEVICE, n bytes: GF_XDP_DROP / GF_XDP_PASS per input frame; may be NULL */
+    uint8_t  *snap;      /* DEVICE, max_out * frames->snap_stride: the XDP_PASS frames, whole rows,
+                            packed in batch order; may be NULL (then len and index must be NULL too) */
+    uint32_t *len;       /* DEVICE, max_out: wire length of each packed frame; NULL only with snap NULL */
+    uint32_t *index;     /* DEVICE, max_out: batch index i of each packed frame; may be NULL */
+    uint32_t  max_out;   /* capacity of snap / len / index in frames */
+    uint32_t *counts;    /* DEVICE, 4 words, required: [0] frames passed, [1] frames dropped,
+                            [2] frames written = min([0], max_out) (0 with snap NULL), [3] 0 */
+} gf_xdp_frames_out;
+int gf_xdp_filter_frames(int prog, const gf_frames *frames, const gf_xdp_frames_out *out, void *stream);
 
 /* ---- standalone LB (bpf/bpf_lb.c, bpf/netdev_config.h) ---- */
 #define GF_LB_F_L3       (1u << 0)   /* LB_L3 */
