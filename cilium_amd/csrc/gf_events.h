@@ -289,9 +289,8 @@ int gf_event_filter_load(const gf_event_filter_cfg *cfg) {
 int gf_event_drain(int filter, const gf_event_ring *ring, uint32_t first, uint32_t max_n, uint32_t flags,
                    uint8_t *out, uint64_t out_bytes, uint32_t *out_off, gf_event_drain_out *res, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(filter);
-    if (!o || o->kind != ObjKind::EventFilter) return -EBADF;
-    auto p = std::static_pointer_cast<EventFilter>(o);
+    auto p = get_as<EventFilter>(filter);
+    if (!p) return -EBADF;
     if (!ring || !ring->records || !ring->count || !res) return -EFAULT;
     if (!out && out_bytes) return -EFAULT;
     if (flags & ~(GF_EVD_F_PACKED | GF_EVD_F_RESET)) return -EINVAL;

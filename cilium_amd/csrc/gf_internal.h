@@ -111,6 +111,7 @@ struct Obj {
 };
 
 struct Map : Obj {
+    static constexpr ObjKind KIND = ObjKind::Map;
     uint32_t type, ksz, vsz, max_entries, flags;
     std::recursive_mutex mu;    // this map's lock (pkg/bpf/map.go:121)
     OrderPt ord;                // device order of the classify calls that bind it
@@ -214,26 +215,30 @@ struct Map : Obj {
 };
 
 struct ProgXdp : Obj {
+    static constexpr ObjKind KIND = ObjKind::ProgXdp;
     gf_xdp_cfg cfg{};
     std::shared_ptr<Map> m4h, m4l, m6h, m6l, lxc;
     DevBuf ff_ws;              // gf_xdp_filter_frames: the tiles' pass counts, then the verdict bytes when the caller takes none
     std::mutex ff_mu;          // one gf_xdp_filter_frames call at a time per handle (its workspace)
-    ProgXdp() : Obj(ObjKind::ProgXdp) {}
+    ProgXdp() : Obj(KIND) {}
 };
 struct ProgLb : Obj {
+    static constexpr ObjKind KIND = ObjKind::ProgLb;
     gf_lb_cfg cfg{};
     std::shared_ptr<Map> lb4, lb6;
     bool has_dstmac = false;       // LB_DSTMAC (gf_lb_prog_set_dstmac; read by gf_lb_classify_frames only)
     uint8_t dstmac[6] = {};
-    ProgLb() : Obj(ObjKind::ProgLb) {}
+    ProgLb() : Obj(KIND) {}
 };
 struct ProgLxc : Obj {
+    static constexpr ObjKind KIND = ObjKind::ProgLxc;
     gf_lxc_cfg cfg{};
     std::shared_ptr<Map> policy, ct4, ct6, cidr4, cidr6, revnat4, revnat6;
     std::shared_ptr<Map> lb4, ipcache, cidr4e, lb6, cidr6e;   // from-container section
-    ProgLxc() : Obj(ObjKind::ProgLxc) {}
+    ProgLxc() : Obj(KIND) {}
 };
 struct PolicyArray : Obj {
+    static constexpr ObjKind KIND = ObjKind::PolicyArray;
     std::map<uint32_t, std::shared_ptr<ProgLxc>> slots;   // lxc_id -> prog
     // device image
     DevBuf d_slot_of_lxc;      // uint16[65536]: 0 = empty, else cfg index + 1
@@ -246,31 +251,35 @@ struct PolicyArray : Obj {
     bool dbg = false;          // a program with GF_LXC_F_DEBUG is bound (gf_policy_array_update)
     std::mutex mu;             // one classify call at a time per array (its device image)
     OrderPt ord;
-    PolicyArray() : Obj(ObjKind::PolicyArray) {}
+    PolicyArray() : Obj(KIND) {}
 };
 
 struct ProgPipe : Obj {
+    static constexpr ObjKind KIND = ObjKind::ProgPipe;
     gf_pipeline_cfg cfg{};
     std::shared_ptr<ProgXdp> xdp;
     std::shared_ptr<ProgLb> lb;
     std::shared_ptr<Map> lxc;
     std::shared_ptr<PolicyArray> policy;
-    ProgPipe() : Obj(ObjKind::ProgPipe) {}
+    ProgPipe() : Obj(KIND) {}
 };
 struct ProgOverlay : Obj {         // bpf_overlay.c: the program on the tunnel device
+    static constexpr ObjKind KIND = ObjKind::ProgOverlay;
     gf_overlay_cfg cfg{};
     std::shared_ptr<Map> lxc;
     std::shared_ptr<PolicyArray> policy;
-    ProgOverlay() : Obj(ObjKind::ProgOverlay) {}
+    ProgOverlay() : Obj(KIND) {}
 };
 struct ProgHost : Obj {            // bpf_netdev.c with FROM_HOST: the program on cilium_host
+    static constexpr ObjKind KIND = ObjKind::ProgHost;
     gf_host_cfg cfg{};
     std::shared_ptr<Map> lxc;
     std::shared_ptr<PolicyArray> policy;
-    ProgHost() : Obj(ObjKind::ProgHost) {}
+    ProgHost() : Obj(KIND) {}
 };
 
 struct ProgRespond : Obj {         // the ARP / ICMPv6 responder tail calls (gf_respond.h)
+    static constexpr ObjKind KIND = ObjKind::ProgRespond;
     gf_respond_cfg cfg{};
     std::shared_ptr<PolicyArray> policy;   // may be null: the node's programs only
     DevBuf d_slot_of, d_ents;  // uint16[65536] slot -> entry + 1; {NODE_MAC, LXC_ID} per program
@@ -278,21 +287,23 @@ struct ProgRespond : Obj {         // the ARP / ICMPv6 responder tail calls (gf_
     bool have_table = false;
     std::mutex mu;             // one gf_respond call at a time per handle (its device table)
     OrderPt ord;
-    ProgRespond() : Obj(ObjKind::ProgRespond) {}
+    ProgRespond() : Obj(KIND) {}
 };
 
 struct ProgTunnel : Obj {          // VXLAN / Geneve on the wire (gf_tunnel.h)
+    static constexpr ObjKind KIND = ObjKind::ProgTunnel;
     gf_tunnel_cfg cfg{};
-    ProgTunnel() : Obj(ObjKind::ProgTunnel) {}
+    ProgTunnel() : Obj(KIND) {}
 };
 
 struct EventFilter : Obj {         // cilium monitor's --type / --from / --to / --related-to (gf_events.h)
+    static constexpr ObjKind KIND = ObjKind::EventFilter;
     uint32_t type_mask = 0;
     bool given[3] = {};            // from, to, related: the flag was given (n != 0)
     std::vector<uint32_t> bits;    // three 65536-bit bitmaps, in that order
     DevBuf d_bits;                 // their device copy, uploaded by the first drain
     std::mutex mu;
-    EventFilter() : Obj(ObjKind::EventFilter) {}
+    EventFilter() : Obj(KIND) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host
@@ -306,7 +317,16 @@ inline uint64_t dev_insert_limit(const Map &m) {
 }
 
 std::shared_ptr<Obj> get_obj(int handle);
-std::shared_ptr<Map> get_map(int handle);
+// The object behind a handle as a T, or null: no such handle, or an object of another kind.
+template <class T>
+std::shared_ptr<T> get_as(int handle) {
+    auto o = get_obj(handle);
+    if (!o || o->kind != T::KIND) return nullptr;
+    return std::static_pointer_cast<T>(o);
+}
+inline std::shared_ptr<Map> get_map(int handle) { return get_as<Map>(handle); }
+// cilium_lxc's shape: endpoint keys (20 B) to endpoint infos (112 B)
+inline bool lxc_map_ok(const Map &m) { return m.ksz == 20 && m.vsz == 112 && !m.is_lpm(); }
 int new_handle(std::shared_ptr<Obj> o);
 uint32_t host_ifindex();
 const gf_node_cfg &node_cfg();

@@ -3444,7 +3444,7 @@ __device__ int host_program(const HostDev &H, FrontLane &L, uint32_t pid) {
 
 // cilium_host's entry.  The record keeps GF_PIPE_F_REV_PROXY itself (bit 4 is not among the
 // bits gf_rec.cls carries), so the host side has handle_policy complete the records by
-// read-modify-write (PassArgs::keep_flags) and not write-only.
+// read-modify-write (PolicyPass::keep_flags) and not write-only.
 template <int NT>
 __global__ __launch_bounds__(NT) void k_host_front(gf_frames fr, const uint32_t *mark, const uint8_t *tc_index,
                                                    HostDev H, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys,
@@ -6375,6 +6375,14 @@ uint32_t stream_grid(uint32_t n, uint32_t per_block = BLOCK) {
 }
 
 int push_map(const std::shared_ptr<Map> &m, hipStream_t s) { return m ? m->push(s) : 0; }
+// bpf_lb's launch descriptor: the service maps (pushed by the caller) and the program's flags
+LbDev lb_dev(const ProgLb &p) {
+    LbDev L{};
+    if (p.lb4) L.s4 = p.lb4->hdesc();
+    if (p.lb6) L.s6 = p.lb6->hdesc();
+    L.flags = p.cfg.flags;
+    return L;
+}
 // The v4 prefixes as DIR-24-8 tables for XdpDev (GF_XDP_DIR24=1: the A/B against
 // the trie walk), when they build.
 void xdp_dir(const std::shared_ptr<Map> &l4, XdpDev &x, hipStream_t s) {
@@ -6503,9 +6511,8 @@ int gf_xdp_prog_load(const gf_xdp_cfg *cfg) {
 
 int gf_xdp_classify(int prog, const gf_pkt_cols *pkts, uint8_t *verdict, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(prog);
-    if (!o || o->kind != ObjKind::ProgXdp) return -EBADF;
-    auto p = std::static_pointer_cast<ProgXdp>(o);
+    auto p = get_as<ProgXdp>(prog);
+    if (!p) return -EBADF;
     int c = check_cols(pkts);
     if (c <= 0) return c;
     if (!verdict) return -EFAULT;
@@ -6594,9 +6601,8 @@ int gf_lb_prog_load(const gf_lb_cfg *cfg) {
 
 int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out, uint8_t *nd6, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(prog);
-    if (!o || o->kind != ObjKind::ProgLb) return -EBADF;
-    auto p = std::static_pointer_cast<ProgLb>(o);
+    auto p = get_as<ProgLb>(prog);
+    if (!p) return -EBADF;
     int c = check_cols(pkts);
     if (c <= 0) return c;
     if (!out) return -EFAULT;
@@ -6608,10 +6614,7 @@ int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out, uint8_t *n
     CallOrder co(s, ML);
     int r;
     if ((r = push_map(p->lb4, s)) || (r = push_map(p->lb6, s))) return r;
-    LbDev L{};
-    if (p->lb4) L.s4 = p->lb4->hdesc();
-    if (p->lb6) L.s6 = p->lb6->hdesc();
-    L.flags = p->cfg.flags;
+    const LbDev L = lb_dev(*p);
     ProfScope ps("k_lb", s);
     hipLaunchKernelGGL(k_lb, dim3(stream_grid(pkts->n)), dim3(BLOCK), 0, s, *pkts, L, out, nd6,
                        (unsigned long long *)stats_sink());
@@ -6698,14 +6701,13 @@ int gf_policy_array_create(void) {
 
 int gf_policy_array_update(int array, uint32_t lxc_id, int prog) {
     std::unique_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(array);
-    if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
+    auto a = get_as<PolicyArray>(array);
+    if (!a) return -EBADF;
     if (lxc_id > 0xffff) return -E2BIG;
-    auto a = std::static_pointer_cast<PolicyArray>(o);
     if (prog) {
-        auto po = get_obj(prog);
-        if (!po || po->kind != ObjKind::ProgLxc) return -EINVAL;
-        a->slots[lxc_id] = std::static_pointer_cast<ProgLxc>(po);
+        auto po = get_as<ProgLxc>(prog);
+        if (!po) return -EINVAL;
+        a->slots[lxc_id] = po;
     } else {
         a->slots.erase(lxc_id);
     }
@@ -6729,19 +6731,38 @@ int gf_policy_array_update(int array, uint32_t lxc_id, int prog) {
 // allocated and the marks cleared by the caller before its first kernel.
 struct TraceWs { DevBuf mark, px, in; };
 static TraceWs &trace_ws() { static const char tag = 0; return cur_ctx().get<TraceWs>(&tag); }
-struct PassArgs {                  // what the pipeline / egress callers pass to their handle_policy pass
-    uint32_t kind;                 // 1 pipeline, 2 egress
-    uint32_t *rlog, *rlog_n;       // egress connection groups: the related-entry log (null: written inline)
-    const uint32_t *rlog_off;      // device word: the run fell back to pair groups (the log is not used)
-    RelSet rs;                     // GF_EG_RSET: the related entries' set (rlog then only marks it in use)
-    bool on;                       // this call traces (a ring is set and a program / the netdev traces)
-    uint32_t nd_trace, nd_ifindex; // pipeline / overlay: 0, or the front's observation point | its final stage << 8
-                                   // (EvSrc::nd_trace); skb->ingress_ifindex
-    const uint8_t *orig;           // egress: the frames as sent
-    const uint16_t *lxc_id;        // egress: the senders
-    bool keep_flags;               // from-host: the front's record holds a flag gf_rec.cls does not carry
+// Who runs a handle_policy pass (the values are EvSrc::kind's).
+enum class PassKind : uint32_t {
+    Plain = 0,                     // gf_policy_ingress_classify(_batches): packet columns in, gf_ingress_out out
+    Frames = 1,                    // a frame entry point (pipeline, from-overlay, from-host): its front packs
+    Egress = 2,                    // the local deliveries of gf_lxc_egress_classify
+};
+// Fills the records and bucket keys itself (a fused front) instead of k_ing_pack.
+using PackFn = std::function<int(const uint16_t *slot_of, gf_rec *rec, uint32_t *keys)>;
+// One handle_policy pass (ingress_run).  Default-constructed: the plain gf_policy_ingress_classify call.
+struct PolicyPass {
+    PassKind kind = PassKind::Plain;
+    gf_ingress_out *out = nullptr; // plain: the verdict records, or
+    uint8_t *pout = nullptr;       // frames / egress: the 24-byte pipeline records to complete
+    PackFn pack;                   // may be empty: k_ing_pack over the columns
+    const uint32_t *ev_len = nullptr;  // the notifications' lengths (null: the len column), frames and their stride;
+    const uint8_t *ev_snap = nullptr;  // ev_stride is wsnap's stride too
+    uint32_t ev_stride = 0;
+    uint8_t *wsnap = nullptr;      // frames handle_policy writes (a proxy redirect's MAC stores), or null
+    bool lru = true;               // the LRU stand-in after the pass
+    bool px_keep = false;          // continue the cilium_proxy log the same call's earlier pass began (px_log_begin)
+    bool prepared = false;         // pack + schedule already built in ws() (ingress_prepare)
+    uint32_t *rlog = nullptr, *rlog_n = nullptr;   // egress connection groups: the related-entry log (null: written inline)
+    const uint32_t *rlog_off = nullptr;            // device word: the run fell back to pair groups (the log is not used)
+    RelSet rs{};                   // GF_EG_RSET: the related entries' set (rlog then only marks it in use)
+    bool on = false;               // frames / egress: this call traces (a ring is set and a program / the netdev traces)
+    uint32_t nd_trace = 0, nd_ifindex = 0;   // pipeline / overlay: 0, or the front's observation point | its final
+                                   // stage << 8 (EvSrc::nd_trace); skb->ingress_ifindex
+    const uint8_t *orig = nullptr;     // egress: the frames as sent
+    const uint16_t *lxc_id = nullptr;  // egress: the senders
+    bool keep_flags = false;       // from-host: the front's record holds a flag gf_rec.cls does not carry
                                    // (GF_PIPE_F_REV_PROXY), so handle_policy completes it by read-modify-write
-    const uint32_t *hmark;         // from-host: the mark column (EvSrc::hmark)
+    const uint32_t *hmark = nullptr;   // from-host: the mark column (EvSrc::hmark)
 };
 static bool array_traces(const std::shared_ptr<PolicyArray> &a) {
     if (!a) return false;
@@ -7516,25 +7537,77 @@ static int noct_mark(const std::shared_ptr<PolicyArray> &a, uint32_t n, hipStrea
     return hip_ok(hipGetLastError(), "k_ing_noct_mark");
 }
 
-// pack (may be empty): fills the records and bucket keys itself (the fused
-// pipeline front) instead of k_ing_pack; pout: pipeline records to complete.
-using PackFn = std::function<int(const uint16_t *slot_of, gf_rec *rec, uint32_t *keys)>;
-static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols *pkts, uint32_t now_sec,
-                       gf_ingress_out *out, hipStream_t s, const PackFn &pack = PackFn(), uint8_t *pout = nullptr,
-                       const uint32_t *ev_len = nullptr, const uint8_t *ev_snap = nullptr, uint32_t ev_stride = 0,
-                       uint8_t *wsnap = nullptr, bool lru = true, bool px_keep = false, bool prepared = false,
-                       const PassArgs *ta = nullptr) {
+// k_ing_pack over the columns: the records and bucket keys of ws() (ingress_run without a front,
+// ingress_prepare).
+static int pack_cols(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols *pkts, hipStream_t s) {
+    Workspace &w = ws();
+    const uint32_t n = pkts->n;
+    ProfScope ps("k_ing_pack", s);
+    hipLaunchKernelGGL(k_ing_pack, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *pkts,
+                       (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p, gf_key_for(n));
+    return hip_ok(hipGetLastError(), "k_ing_pack");
+}
+
+// What the launches of k_ing_groups / k_ing_groups_dbg over the two families share.
+struct IngLaunch {
+    uint32_t grid;
+    hipStream_t s;
+    const Workspace &w;
+    const IngCtx &X;
+    gf_ingress_out *out;
+    unsigned long long *sink;
+    uint4 *dlog;                   // a program with DEBUG: the instantiations that log (else null)
+    bool pct;                      // per-endpoint CT maps (ConntrackLocal)
+    bool pol_wave;                 // the egress deliveries' pass (single-packet buckets): IPv4 only, IPv6 has
+                                   // no such instantiation and runs the plain kernel
+};
+// One family's launch; cnt: the family's CT map's count word (non-strict mode accounts the kernel's
+// net element change there), null with per-endpoint maps.
+template <int FAM>
+static void launch_ing_groups(const IngLaunch &g, uint32_t *cnt) {
+    const Workspace &w = g.w;
+    auto go = [&](auto kern, auto... dlog) {
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(BLOCK), 0, g.s, g.X, (uint32_t *)w.sched.p, (const uint2 *)w.order.p,
+                           (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, g.out, cnt, g.sink,
+                           dlog...);
+    };
+    ProfScope ps(FAM == 6 ? "k_ing_groups6" : "k_ing_groups", g.s);
+    if (g.dlog && g.pct) go(k_ing_groups_dbg<FAM, true>, g.dlog);
+    else if (g.dlog) go(k_ing_groups_dbg<FAM, false>, g.dlog);
+    else if (g.pct) go(k_ing_groups<FAM, 1, true>);
+    else if (FAM == 4 && g.pol_wave) go(k_ing_groups<4, GF_GRAB_ING, false, true>);
+    else go(k_ing_groups<FAM>);
+}
+
+// handle_policy over a batch: the program table, the CT maps' accounting, the flow-group schedule,
+// the group kernels, then the proxy log, the notifications and the LRU stand-in.
+static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols *pkts, uint32_t now_sec, hipStream_t s,
+                       const PolicyPass &P) {
     int r;
+    const bool plain = P.kind == PassKind::Plain, egress = P.kind == PassKind::Egress;
+    // the frame fronts and the egress front write saddr6 | daddr6 of a packet as one 32-B piece;
+    // the plain call reads two columns
+    const uint32_t a6_stride = plain ? 16u : 32u;
+    // the frame fronts' keys (gf_key_for(n, true))
+    const bool wide = P.kind == PassKind::Frames;
+    // the egress deliveries' pass: single-packet buckets in packet-index order, the IPv4 kernel that
+    // takes them a wave at a time
+    const bool pol_wave = egress;
+    // a frame entry's records are written whole (no read-modify-write) unless its front left a flag
+    // in them (keep_flags)
+    const bool pout_wo = GF_POUT_WO && P.pout && P.kind == PassKind::Frames && !P.keep_flags;
     const int noct = array_noct(a);                     // programs without conntrack: 0 none, 1 some, 2 all
-    if (noct && ta && ta->kind == 2) return -EOPNOTSUPP;   // (the egress entry point refuses such arrays)
-    // trace notifications: the plain ingress call decides here, the pipeline and
-    // egress callers (whose earlier kernels mark packets) pass their decision
-    const bool tracing = ta ? ta->on : (event_ring().records && array_traces(a));
-    if (tracing && !ta && (r = trace_prepare(pkts->n, false, s))) return r;
-    // debug notifications (GF_LXC_F_DEBUG): the plain ingress call only; every other entry
-    // point (ta non-null) runs such programs as if the flag were clear
-    const bool debugging = !ta && event_ring().records && a->dbg && noct != 2;
+    if (noct && egress) return -EOPNOTSUPP;             // (the egress entry point refuses such arrays)
+    // trace notifications: the plain call decides and prepares here, the frame and egress
+    // callers (whose earlier kernels mark packets) pass their decision
+    const bool tracing = plain ? event_ring().records && array_traces(a) : P.on;
+    if (tracing && plain && (r = trace_prepare(pkts->n, false, s))) return r;
+    // debug notifications (GF_LXC_F_DEBUG): the plain call only; every other entry point runs
+    // such programs as if the flag were clear
+    const bool debugging = plain && event_ring().records && a->dbg && noct != 2;
     if (debugging && (r = dbg_prepare(pkts->n, s))) return r;
+    gf_ingress_out *const out = P.out;
+    uint8_t *const pout = P.pout;
     // 1. sync tables, build the device program table
     std::vector<std::shared_ptr<ProgLxc>> progs;
     host_mark("ing");
@@ -7563,25 +7636,20 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     // A family with a HASH map that could fill: one bucket, in batch order (a schedule
     // built ahead of the call is rebuilt here)
     const uint32_t serial = n > 1 && noct != 2 ? ct_serial_fams(cm) : 0u;
-    if (serial) prepared = false;
+    const bool prepared = P.prepared && !serial;
     Workspace &w = ws();
     if (prepared) {
         // pack + schedule already built in ws() (ingress_prepare)
     } else if ((r = ws_grow(n))) {
         return r;
-    } else if (pack) {
-        if ((r = pack((const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p))) return r;
-    } else {
-        ProfScope ps("k_ing_pack", s);
-        hipLaunchKernelGGL(k_ing_pack, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *pkts,
-                           (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p,
-                           (uint32_t *)w.keys.p, gf_key_for(n));
-        if ((r = hip_ok(hipGetLastError(), "k_ing_pack"))) return r;
+    } else if (P.pack) {
+        if ((r = P.pack((const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p))) return r;
+    } else if ((r = pack_cols(a, pkts, s))) {
+        return r;
     }
     host_mark("pack");
     // Programs without conntrack: their packets leave the schedule (mixed array), or
     // there is no schedule at all (every program; k_ing_noct alone, below)
-    const bool wide = ta && ta->kind == 1;              // the frame fronts' keys (gf_key_for(n, true))
     if (noct == 1 && !prepared && (r = noct_mark(a, n, s, wide))) return r;
     if (serial) {
         ProfScope ps("k_ing_serial_keys", s);
@@ -7589,79 +7657,35 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
                            gf_key_for(n, wide), serial);
         if ((r = hip_ok(hipGetLastError(), "k_ing_serial_keys"))) return r;
     }
-    if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, ta && ta->kind == 2, wide))) return r;
+    if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, egress, wide))) return r;
     host_mark("sched");
-    uint32_t *d_sched = (uint32_t *)w.sched.p;
     // 4. handle_policy: one bucket per lane, buckets from the longest-first queue
     IngCtx X{};
     X.cfgs = (const gf_lxc_dev *)a->d_cfgs.p;
     X.saddr6 = pkts->saddr6; X.daddr6 = pkts->daddr6;
-    X.a6_stride = ta ? 32u : 16u;                       // the pipeline's / egress' interleaved addresses
+    X.a6_stride = a6_stride;
     if (ct4m) X.ct4 = cfg_ct4;
     if (ct6m) X.ct6 = cfg_ct6;
     X.now = now_sec; X.host_ifindex = host_ifindex();
     X.strict = strict;
     X.pout = pout;
-    X.pout_wo = GF_POUT_WO && pout && ta && ta->kind == 1 && !ta->keep_flags ? 1u : 0u;
-    X.pol_wave = ta && ta->kind == 2 ? 1u : 0u;
-    X.snap = wsnap; X.snap_stride = ev_stride;
+    X.pout_wo = pout_wo ? 1u : 0u;
+    X.pol_wave = pol_wave ? 1u : 0u;
+    X.snap = P.wsnap; X.snap_stride = P.ev_stride;
     const gf_node_cfg &node = node_cfg();
     X.gw = node.ipv4_gateway;
     memcpy(X.host6, node.host_ip6, 16);
     if (tracing) { X.tmark = (uint8_t *)trace_ws().mark.p; X.tcap = (uint8_t *)trace_ws().px.p; }
-    if (ta) { X.rlog = ta->rlog; X.rlog_n = ta->rlog_n; X.rlog_off = ta->rlog_off; X.rs = ta->rs; }
-    uint4 *dlog = debugging ? (uint4 *)dbg_ws().log.p : nullptr;
-    if ((r = px_log_begin(n, s, X, px_keep))) return r;
-    // Non-strict mode accounts each kernel's net element change into its family's map.
-    uint32_t *cnt4 = ct4m ? (uint32_t *)ct4m->d_count.p : nullptr, *cnt6 = ct6m ? (uint32_t *)ct6m->d_count.p : nullptr;
+    X.rlog = P.rlog; X.rlog_n = P.rlog_n; X.rlog_off = P.rlog_off; X.rs = P.rs;
+    if ((r = px_log_begin(n, s, X, P.px_keep))) return r;
     unsigned long long *sink = (unsigned long long *)stats_sink();
     if (noct != 2) {
         // resident-grid launches: every wave loops on its family's queue until it is drained
-        uint32_t grid = resident_blocks(8);
-        uint32_t need = (n + BLOCK - 1) / BLOCK;
-        if (grid > need) grid = need;
-        {
-            ProfScope ps("k_ing_groups", s);
-            if (debugging && cm.pct)                    // a program with DEBUG: the instantiations that log
-                hipLaunchKernelGGL((k_ing_groups_dbg<4, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
-                                   nullptr, sink, dlog);
-            else if (debugging)
-                hipLaunchKernelGGL((k_ing_groups_dbg<4, false>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
-                                   cnt4, sink, dlog);
-            else if (cm.pct)                            // per-endpoint CT maps (ConntrackLocal)
-                hipLaunchKernelGGL((k_ing_groups<4, 1, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
-                                   nullptr, sink);
-            else if (X.pol_wave)                        // the egress deliveries' pass (single-packet buckets)
-                hipLaunchKernelGGL((k_ing_groups<4, GF_GRAB_ING, false, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out, cnt4,
-                                   sink);
-            else
-                hipLaunchKernelGGL(k_ing_groups<4>, dim3(grid), dim3(BLOCK), 0, s, X, d_sched, (const uint2 *)w.order.p,
-                                   (const uint32_t *)w.perm.p,
-                                   (const gf_rec *)w.rec.p, out, cnt4, sink);
-        }
-        if (pkts->saddr6) {    // IPv6 packets reach conntrack only with v6 columns
-            ProfScope ps("k_ing_groups6", s);
-            if (debugging && cm.pct)
-                hipLaunchKernelGGL((k_ing_groups_dbg<6, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
-                                   nullptr, sink, dlog);
-            else if (debugging)
-                hipLaunchKernelGGL((k_ing_groups_dbg<6, false>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
-                                   cnt6, sink, dlog);
-            else if (cm.pct)
-                hipLaunchKernelGGL((k_ing_groups<6, 1, true>), dim3(grid), dim3(BLOCK), 0, s, X, d_sched,
-                                   (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const gf_rec *)w.rec.p, out,
-                                   nullptr, sink);
-            else
-                hipLaunchKernelGGL(k_ing_groups<6>, dim3(grid), dim3(BLOCK), 0, s, X, d_sched, (const uint2 *)w.order.p,
-                                   (const uint32_t *)w.perm.p,
-                                   (const gf_rec *)w.rec.p, out, cnt6, sink);
-        }
+        const uint32_t grid = std::min(resident_blocks(8), (n + BLOCK - 1) / BLOCK);
+        const IngLaunch g{grid, s, w, X, out, sink, debugging ? (uint4 *)dbg_ws().log.p : nullptr, cm.pct, pol_wave};
+        launch_ing_groups<4>(g, ct4m ? (uint32_t *)ct4m->d_count.p : nullptr);
+        // IPv6 packets reach conntrack only with v6 columns
+        if (pkts->saddr6) launch_ing_groups<6>(g, ct6m ? (uint32_t *)ct6m->d_count.p : nullptr);
     }
     if ((r = hip_ok(hipGetLastError(), "k_ing_groups"))) return r;
     if (noct) {
@@ -7671,28 +7695,25 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
         if ((r = hip_ok(hipGetLastError(), "k_ing_noct"))) return r;
     }
     host_mark("groups");
-    if ((r = px_log_apply(X, s, wsnap, ev_len ? ev_len : pkts->len, ev_stride, pout ? pout : (uint8_t *)out,
-                          pout != nullptr, n)))
-        return r;
+    const uint32_t *ev_len = P.ev_len ? P.ev_len : pkts->len;
+    if ((r = px_log_apply(X, s, P.wsnap, ev_len, P.ev_stride, pout ? pout : (uint8_t *)out, pout != nullptr, n))) return r;
     {
         EvSrc E{};
         E.recs = pout ? pout : (const uint8_t *)out;
         E.stride = pout ? 24u : 8u; E.act_off = pout ? 1u : 0u; E.stage_off = pout ? 0 : -1;
         E.prec = (const gf_rec *)w.rec.p; E.cfgs = (const gf_lxc_dev *)a->d_cfgs.p;
-        E.len = ev_len ? ev_len : pkts->len; E.flow_hash = pkts->flow_hash; E.n = n;
-        E.snap = ev_snap; E.snap_stride = ev_stride;
+        E.len = ev_len; E.flow_hash = pkts->flow_hash; E.n = n;
+        E.snap = P.ev_snap; E.snap_stride = P.ev_stride;
         if (tracing) {
             const TraceWs &t = trace_ws();
-            E.trace = 1; E.kind = ta ? ta->kind : 0u;
+            E.trace = 1; E.kind = (uint32_t)P.kind;
             E.tmark = (const uint8_t *)t.mark.p; E.tcap_px = (const uint8_t *)t.px.p;
             E.tcap_in = (const uint8_t *)t.in.p;
             E.host_ifindex = host_ifindex(); E.encap_ifindex = node.encap_ifindex;
-            if (ta) {
-                E.nd_trace = ta->nd_trace; E.nd_ifindex = ta->nd_ifindex;
-                E.orig = ta->orig; E.lxc_id = ta->lxc_id;
-                E.hmark = ta->hmark;
-                E.slot_of = (const uint16_t *)a->d_slot_of_lxc.p;
-            }
+            E.nd_trace = P.nd_trace; E.nd_ifindex = P.nd_ifindex;
+            E.orig = P.orig; E.lxc_id = P.lxc_id;
+            E.hmark = P.hmark;
+            if (!plain) E.slot_of = (const uint16_t *)a->d_slot_of_lxc.p;
         }
         if (debugging) { E.dlog = (const uint4 *)dbg_ws().log.p; E.tc_index = pkts->tc_index; E.host_ifindex = host_ifindex(); }
         if ((r = emit_drop_events(E, s, debugging))) return r;
@@ -7701,7 +7722,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     for (auto &p : progs) {
         if (p->policy) p->policy->device_modified();
     }
-    if (lru && ((r = lru_evict_maps(cm.m4, now_sec, s)) || (r = lru_evict_maps(cm.m6, now_sec, s)))) return r;
+    if (P.lru && ((r = lru_evict_maps(cm.m4, now_sec, s)) || (r = lru_evict_maps(cm.m6, now_sec, s)))) return r;
     host_mark("lru");
     for (auto *v : {&cm.m4, &cm.m6})
         for (auto &m : *v) m->device_modified();
@@ -7711,20 +7732,12 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
 // The stateless half of ingress_run (k_ing_pack + the flow-group schedule) into ws().
 static int ingress_prepare(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols *pkts, hipStream_t s) {
     const uint32_t n = pkts->n;
-    Workspace &w = ws();
     int r;
-    if ((r = ws_grow(n))) return r;
-    {
-        ProfScope ps("k_ing_pack", s);
-        hipLaunchKernelGGL(k_ing_pack, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, *pkts,
-                           (const uint16_t *)a->d_slot_of_lxc.p, (gf_rec *)w.rec.p, (uint32_t *)w.keys.p,
-                           gf_key_for(n));
-        if ((r = hip_ok(hipGetLastError(), "k_ing_pack"))) return r;
-    }
+    if ((r = ws_grow(n)) || (r = pack_cols(a, pkts, s))) return r;
     const int noct = array_noct(a);
     if (noct == 2) return 0;                            // no program with conntrack: no schedule
     if (noct == 1 && (r = noct_mark(a, n, s))) return r;
-    return schedule_groups(n, s, (const gf_rec *)w.rec.p);
+    return schedule_groups(n, s, (const gf_rec *)ws().rec.p);
 }
 
 // The stream that builds the next batch's schedule, and the events between the two.
@@ -7776,16 +7789,28 @@ static EncapDev encap_dev(const gf_node_cfg &node, const std::shared_ptr<Map> &t
     return d;
 }
 
-// A front kernel's launch: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B
+// A frame kernel's launch: 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B
 // (<= 32 KiB of LDS rows), one tile per block
 struct FrontLaunch {
     uint32_t nt, grid;
     size_t lds;
     hipStream_t s;
-    uint8_t *s6, *d6;              // saddr6 | daddr6 per packet in one 32-B piece (IngCtx::a6_stride 32)
     unsigned long long *sink;
-    gf_key_cfg K;
+    uint8_t *s6, *d6;              // the fronts: saddr6 | daddr6 per packet in one 32-B piece (IngCtx::a6_stride 32)
+    gf_key_cfg K;                  // the fronts: the bucket keys' width
 };
+// The geometry over fr.  vec_copy: the kernel's snap copy in 16-B pieces (the stride and both
+// buffers allow it).
+static FrontLaunch front_geometry(const gf_frames &fr, const uint8_t *snap_out, hipStream_t s, uint32_t &vec_copy) {
+    FrontLaunch f{};
+    f.nt = fr.snap_stride <= 128 ? 256u : 128u;
+    f.grid = (fr.n + f.nt - 1) / f.nt;
+    f.lds = (size_t)f.nt * fr.snap_stride;
+    f.s = s;
+    f.sink = (unsigned long long *)stats_sink();
+    vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
+    return f;
+}
 template <class Kern, class... A>
 static void launch_nt(Kern k256, Kern k128, const FrontLaunch &f, A... args) {
     if (f.nt == 256) hipLaunchKernelGGL(k256, dim3(f.grid), dim3(256), f.lds, f.s, args...);
@@ -7794,43 +7819,42 @@ static void launch_nt(Kern k256, Kern k128, const FrontLaunch &f, A... args) {
 
 // A frame entry point's run, under the caller's locks and after frames_check: the launch
 // geometry, the IPv6 address buffer, the trace set-up, then ingress_run with launch(f, slot_of,
-// rec, keys) as its front.  trace: the program's TR_FROM_* | its stage << 8 when it traces,
-// else 0.  vec_copy / tcap_in: the entry descriptor's fields, set here before the launch.
+// rec, keys) as its front.  pass: the entry's own fields set (keep_flags, hmark), the rest filled
+// here.  trace: the program's TR_FROM_* | its stage << 8 when it traces, else 0.  vec_copy /
+// tcap_in: the entry descriptor's fields, set here before the launch.
 template <class Launch>
 static int front_call(const std::shared_ptr<PolicyArray> &policy, const gf_frames &fr, const uint32_t *flow_hash,
-                      uint32_t now_sec, gf_pipeline_out *out, uint8_t *snap_out, hipStream_t s, PassArgs &ta,
+                      uint32_t now_sec, gf_pipeline_out *out, uint8_t *snap_out, hipStream_t s, PolicyPass &pass,
                       uint32_t trace, uint32_t ifindex, uint32_t &vec_copy, uint8_t *&tcap_in, const char *kernel,
                       Launch launch) {
     int r;
     const uint32_t n = fr.n;
-    FrontLaunch f{};
-    f.nt = fr.snap_stride <= 128 ? 256u : 128u;
-    f.grid = (n + f.nt - 1) / f.nt;
-    f.lds = (size_t)f.nt * fr.snap_stride;
-    f.s = s;
+    FrontLaunch f = front_geometry(fr, snap_out, s, vec_copy);
     PipeWs &w = pipe_ws();
     if (w.s6.bytes < (size_t)n * 32 && (r = w.s6.ensure((size_t)n * 32))) return r;
     f.s6 = (uint8_t *)w.s6.p; f.d6 = f.s6 + 16;
-    f.sink = (unsigned long long *)stats_sink();
     f.K = gf_key_for(n, true);
-    vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
-    ta.kind = 1;                                       // records completed as the pipeline's
-    ta.nd_trace = trace;
-    ta.nd_ifindex = ifindex;
-    ta.on = event_ring().records && (ta.nd_trace || array_traces(policy));
-    if (ta.on && (r = trace_prepare(n, ta.nd_trace != 0, s))) return r;
-    if (ta.on && ta.nd_trace) tcap_in = (uint8_t *)trace_ws().in.p;
+    pass.kind = PassKind::Frames;                      // records completed as the pipeline's
+    pass.nd_trace = trace;
+    pass.nd_ifindex = ifindex;
+    pass.on = event_ring().records && (trace || array_traces(policy));
+    if (pass.on && (r = trace_prepare(n, trace != 0, s))) return r;
+    if (pass.on && trace) tcap_in = (uint8_t *)trace_ws().in.p;
     gf_pkt_cols c2{};
     c2.n = n;
     c2.saddr6 = f.s6; c2.daddr6 = f.d6;
     c2.flow_hash = flow_hash;
-    auto front = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
+    pass.pack = [&](const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) -> int {
         ProfScope ps(kernel, s);
         launch(f, slot_of, rec, keys);
         return hip_ok(hipGetLastError(), kernel);
     };
-    return ingress_run(policy, &c2, now_sec, nullptr, s, front, (uint8_t *)out, fr.len,
-                       snap_out ? snap_out : fr.snap, fr.snap_stride, snap_out, true, false, false, &ta);
+    pass.pout = (uint8_t *)out;
+    pass.ev_len = fr.len;
+    pass.ev_snap = snap_out ? snap_out : fr.snap;
+    pass.ev_stride = fr.snap_stride;
+    pass.wsnap = snap_out;
+    return ingress_run(policy, &c2, now_sec, s, pass);
 }
 
 extern "C" {
@@ -7838,9 +7862,8 @@ extern "C" {
 int gf_policy_ingress_classify_batches(int array, uint32_t nb, const gf_pkt_cols *const *batches,
                                        const uint32_t *now_sec, gf_ingress_out *const *outs, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(array);
-    if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
-    auto a = std::static_pointer_cast<PolicyArray>(o);
+    auto a = get_as<PolicyArray>(array);
+    if (!a) return -EBADF;
     if (nb && (!batches || !now_sec || !outs)) return -EFAULT;
     for (uint32_t k = 0; k < nb; k++) {
         const int c = check_cols(batches[k]);
@@ -7878,8 +7901,10 @@ int gf_policy_ingress_classify_batches(int array, uint32_t nb, const gf_pkt_cols
         if (hip_ok(hipStreamWaitEvent(s, P.built[slot], 0), "wait built")) return -EIO;
         if (batches[k]->n) {
             cur_ctx().ws_slot = slot;
-            r = ingress_run(a, batches[k], now_sec[k], outs[k], s, PackFn(), nullptr, nullptr, nullptr, 0, nullptr,
-                            true, false, true);
+            PolicyPass pass;
+            pass.out = outs[k];
+            pass.prepared = true;                         // (prep(k) built the schedule)
+            r = ingress_run(a, batches[k], now_sec[k], s, pass);
             cur_ctx().ws_slot = 0;
             if (r) return r;
         }
@@ -7891,9 +7916,8 @@ int gf_policy_ingress_classify_batches(int array, uint32_t nb, const gf_pkt_cols
 int gf_policy_ingress_classify(int array, const gf_pkt_cols *pkts, uint32_t now_sec, gf_ingress_out *out,
                                void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(array);
-    if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
-    auto a = std::static_pointer_cast<PolicyArray>(o);
+    auto a = get_as<PolicyArray>(array);
+    if (!a) return -EBADF;
     int c = check_cols(pkts);
     if (c <= 0) return c;
     if (!out) return -EFAULT;
@@ -7904,7 +7928,9 @@ int gf_policy_ingress_classify(int array, const gf_pkt_cols *pkts, uint32_t now_
     lock_array_maps(L, a);
     L.lock();
     CallOrder co((hipStream_t)stream, L, a.get());
-    return ingress_run(a, pkts, now_sec, out, (hipStream_t)stream);
+    PolicyPass pass;
+    pass.out = out;
+    return ingress_run(a, pkts, now_sec, (hipStream_t)stream, pass);
 }
 
 // ---- full pipeline ----
@@ -7914,24 +7940,21 @@ int gf_pipeline_load(const gf_pipeline_cfg *cfg) {
     auto p = std::make_shared<ProgPipe>();
     p->cfg = *cfg;
     if (cfg->xdp_prog) {
-        auto o = get_obj(cfg->xdp_prog);
-        if (!o || o->kind != ObjKind::ProgXdp) return -EBADF;
-        p->xdp = std::static_pointer_cast<ProgXdp>(o);
+        p->xdp = get_as<ProgXdp>(cfg->xdp_prog);
+        if (!p->xdp) return -EBADF;
     }
     if (cfg->lb_prog) {
-        auto o = get_obj(cfg->lb_prog);
-        if (!o || o->kind != ObjKind::ProgLb) return -EBADF;
-        p->lb = std::static_pointer_cast<ProgLb>(o);
+        p->lb = get_as<ProgLb>(cfg->lb_prog);
+        if (!p->lb) return -EBADF;
     }
     auto m = get_map(cfg->netdev.lxc_map);
     if (!m) return -EBADF;
-    if (m->ksz != 20 || m->vsz != 112 || m->is_lpm()) return -EINVAL;
+    if (!lxc_map_ok(*m)) return -EINVAL;
     p->lxc = m;
     // ENCAP_IFINDEX for the netdev stage is the node's: it must be defined, with a tunnel map to look up
     if ((cfg->netdev.flags & GF_NETDEV_F_ENCAP) && (!node_cfg().encap_ifindex || !node_map(2))) return -EINVAL;
-    auto a = get_obj(cfg->policy_array);
-    if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
-    p->policy = std::static_pointer_cast<PolicyArray>(a);
+    p->policy = get_as<PolicyArray>(cfg->policy_array);
+    if (!p->policy) return -EBADF;
     return new_handle(p);
 }
 
@@ -7943,9 +7966,8 @@ int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_
 int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_pipeline_out *out,
                                 uint8_t *nd6, uint8_t *snap_out, uint32_t *tunnel_ip, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(pipe);
-    if (!o || o->kind != ObjKind::ProgPipe) return -EBADF;
-    auto p = std::static_pointer_cast<ProgPipe>(o);
+    auto p = get_as<ProgPipe>(pipe);
+    if (!p) return -EBADF;
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
     int r = frames_check(fr, out != nullptr);
@@ -7978,9 +8000,7 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
     }
     if (p->lb) {
         if ((r = push_map(p->lb->lb4, s)) || (r = push_map(p->lb->lb6, s))) return r;
-        if (p->lb->lb4) P.L.s4 = p->lb->lb4->hdesc();
-        if (p->lb->lb6) P.L.s6 = p->lb->lb6->hdesc();
-        P.L.flags = p->lb->cfg.flags;
+        P.L = lb_dev(*p->lb);
         P.lb_redirect_ifindex = p->lb->cfg.redirect_ifindex;
         P.has_lb = 1;
     }
@@ -8006,9 +8026,9 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
     } else if (tunnel_ip) {
         if (hip_ok(hipMemsetAsync(tunnel_ip, 0, (size_t)fr.n * 4, s), "tunnel_ip")) return -EIO;
     }
-    PassArgs ta{};
+    PolicyPass pass;
     const uint32_t trace = (nd.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_STACK | (GF_STAGE_NETDEV << 8)) : 0u;
-    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, ta, trace, nd.ingress_ifindex, P.vec_copy,
+    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, pass, trace, nd.ingress_ifindex, P.vec_copy,
                       P.tcap_in, ndx ? "k_nd_front" : "k_pipe_front",
                       [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
         if (ndx)
@@ -8023,9 +8043,8 @@ int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_s
 // ---- bpf_lb over frames ----
 int gf_lb_prog_set_dstmac(int prog, const uint8_t mac[6]) {
     std::unique_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(prog);
-    if (!o || o->kind != ObjKind::ProgLb) return -EBADF;
-    auto p = std::static_pointer_cast<ProgLb>(o);
+    auto p = get_as<ProgLb>(prog);
+    if (!p) return -EBADF;
     if (!(p->cfg.flags & GF_LB_F_REDIRECT)) return -EINVAL;   // LB_DSTMAC sits inside #ifdef LB_REDIRECT
     p->has_dstmac = mac != nullptr;
     if (mac) memcpy(p->dstmac, mac, 6); else memset(p->dstmac, 0, 6);
@@ -8035,9 +8054,8 @@ int gf_lb_prog_set_dstmac(int prog, const uint8_t mac[6]) {
 int gf_lb_classify_frames(int prog, const gf_frames *frames, const uint32_t *flow_hash, gf_lb_out *out,
                           uint8_t *nd6, uint8_t *snap_out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(prog);
-    if (!o || o->kind != ObjKind::ProgLb) return -EBADF;
-    auto p = std::static_pointer_cast<ProgLb>(o);
+    auto p = get_as<ProgLb>(prog);
+    if (!p) return -EBADF;
     if (!frames) return -EFAULT;
     const gf_frames &fr = *frames;
     int r = frames_check(fr, out != nullptr);
@@ -8049,29 +8067,17 @@ int gf_lb_classify_frames(int prog, const gf_frames *frames, const uint32_t *flo
     ML.lock();
     CallOrder co(s, ML);
     if ((r = push_map(p->lb4, s)) || (r = push_map(p->lb6, s))) return r;
-    LbDev L{};
-    if (p->lb4) L.s4 = p->lb4->hdesc();
-    if (p->lb6) L.s6 = p->lb6->hdesc();
-    L.flags = p->cfg.flags;
+    const LbDev L = lb_dev(*p);
     LbFrDev F{};
     if (p->has_dstmac) {
         F.has_mac = 1;
         memcpy(&F.mac_lo, p->dstmac, 4);
         F.mac_hi = (uint32_t)p->dstmac[4] | ((uint32_t)p->dstmac[5] << 8);
     }
-    F.vec_copy = (fr.snap_stride % 16 == 0) && (((uintptr_t)fr.snap | (uintptr_t)snap_out) & 15u) == 0;
-    // 256 lanes per block up to 128-B snaps, 128 lanes up to 256 B (<= 32 KiB of LDS rows), as the fronts
-    const uint32_t nt = fr.snap_stride <= 128 ? 256u : 128u;
-    const uint32_t grid = (fr.n + nt - 1) / nt;
-    const size_t lds = (size_t)nt * fr.snap_stride;
+    const FrontLaunch f = front_geometry(fr, snap_out, s, F.vec_copy);   // the fronts' tiles
     {
         ProfScope ps("k_lb_frames", s);
-        if (nt == 256)
-            hipLaunchKernelGGL(k_lb_frames<256>, dim3(grid), dim3(256), lds, s, fr, flow_hash, L, F, out, nd6, snap_out,
-                               (unsigned long long *)stats_sink());
-        else
-            hipLaunchKernelGGL(k_lb_frames<128>, dim3(grid), dim3(128), lds, s, fr, flow_hash, L, F, out, nd6, snap_out,
-                               (unsigned long long *)stats_sink());
+        launch_nt(k_lb_frames<256>, k_lb_frames<128>, f, fr, flow_hash, L, F, out, nd6, snap_out, f.sink);
         if ((r = hip_ok(hipGetLastError(), "k_lb_frames"))) return r;
     }
     // send_drop_notify_error's records (bpf_lb.c:194-195): the drop list of ev_list without a trace.
@@ -8094,11 +8100,10 @@ int gf_overlay_load(const gf_overlay_cfg *cfg) {
     p->cfg = *cfg;
     auto m = get_map(cfg->lxc_map);
     if (!m) return -EBADF;
-    if (m->ksz != 20 || m->vsz != 112 || m->is_lpm()) return -EINVAL;
+    if (!lxc_map_ok(*m)) return -EINVAL;
     p->lxc = m;
-    auto a = get_obj(cfg->policy_array);
-    if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
-    p->policy = std::static_pointer_cast<PolicyArray>(a);
+    p->policy = get_as<PolicyArray>(cfg->policy_array);
+    if (!p->policy) return -EBADF;
     return new_handle(p);
 }
 
@@ -8106,9 +8111,8 @@ int gf_overlay_load(const gf_overlay_cfg *cfg) {
 static int overlay_call(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts *opts, bool with_opts,
                         uint32_t now_sec, gf_pipeline_out *out, uint8_t *snap_out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(ovl);
-    if (!o || o->kind != ObjKind::ProgOverlay) return -EBADF;
-    auto p = std::static_pointer_cast<ProgOverlay>(o);
+    auto p = get_as<ProgOverlay>(ovl);
+    if (!p) return -EBADF;
     if (!b) return -EFAULT;
     const bool geneve = p->cfg.flags & GF_OVERLAY_F_GENEVE;
     if (geneve && !with_opts) return -EINVAL;          // ENCAP_GENEVE reads options: gf_overlay_classify_opts
@@ -8137,9 +8141,9 @@ static int overlay_call(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts
     const gf_node_cfg &node = node_cfg();
     O.host_ifindex = node.host_ifindex;
     memcpy(O.host_mac, node.host_mac, 6); memcpy(O.node_mac, node.node_mac, 6);
-    PassArgs ta{};
+    PolicyPass pass;
     const uint32_t trace = (p->cfg.flags & GF_OVERLAY_F_TRACE_NOTIFY) ? (TR_FROM_OVERLAY | (GF_STAGE_OVERLAY << 8)) : 0u;
-    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, ta, trace, p->cfg.ingress_ifindex, O.vec_copy,
+    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, pass, trace, p->cfg.ingress_ifindex, O.vec_copy,
                       O.tcap_in, "k_ovl_front",
                       [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
         if (geneve)
@@ -8165,9 +8169,8 @@ int gf_overlay_classify_opts(int ovl, const gf_overlay_batch *b, const gf_tunnel
 int gf_lxc_egress_tunnel_meta(int policy_array, const uint16_t *lxc_id, const gf_egress_out *records, uint32_t n,
                               uint32_t *tunnel_id, uint8_t *opt, uint8_t *opt_len, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(policy_array);
-    if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
-    auto a = std::static_pointer_cast<PolicyArray>(o);
+    auto a = get_as<PolicyArray>(policy_array);
+    if (!a) return -EBADF;
     if (n == 0) return 0;
     if (!lxc_id || !records || !tunnel_id || !opt || !opt_len) return -EFAULT;
     if ((uintptr_t)opt & 3u) return -EINVAL;           // written as two words per packet (gf_tunnel_opts' alignment)
@@ -8197,20 +8200,18 @@ int gf_host_load(const gf_host_cfg *cfg) {
     p->cfg = *cfg;
     auto m = get_map(cfg->netdev.lxc_map);
     if (!m) return -EBADF;
-    if (m->ksz != 20 || m->vsz != 112 || m->is_lpm()) return -EINVAL;
+    if (!lxc_map_ok(*m)) return -EINVAL;
     p->lxc = m;
-    auto a = get_obj(cfg->policy_array);
-    if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
-    p->policy = std::static_pointer_cast<PolicyArray>(a);
+    p->policy = get_as<PolicyArray>(cfg->policy_array);
+    if (!p->policy) return -EBADF;
     return new_handle(p);
 }
 
 int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipeline_out *out,
                      uint8_t *snap_out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(host);
-    if (!o || o->kind != ObjKind::ProgHost) return -EBADF;
-    auto p = std::static_pointer_cast<ProgHost>(o);
+    auto p = get_as<ProgHost>(host);
+    if (!p) return -EBADF;
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
     int r = frames_check(fr, out != nullptr);
@@ -8237,11 +8238,11 @@ int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipe
     H.flags = nd.flags; H.fixed_secctx = nd.fixed_secctx;
     memcpy(H.router6, nd.router_ip6, 8);
     memcpy(H.net_mac, p->cfg.cilium_net_mac, 6);
-    PassArgs ta{};
-    ta.keep_flags = true;
-    ta.hmark = b->mark;
+    PolicyPass pass;
+    pass.keep_flags = true;
+    pass.hmark = b->mark;
     const uint32_t trace = (nd.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_HOST | (GF_STAGE_HOST << 8)) : 0u;
-    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, ta, trace, nd.ingress_ifindex, H.vec_copy,
+    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, pass, trace, nd.ingress_ifindex, H.vec_copy,
                       H.tcap_in, "k_host_front",
                       [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
         launch_nt(k_host_front<256>, k_host_front<128>, f, fr, b->mark, b->tc_index, H, slot_of, rec, keys, f.s6, f.d6, out,
@@ -8253,9 +8254,8 @@ int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipe
 int gf_pipeline_partition(int pipe, const gf_pipe_batch *b, uint32_t self_rank, uint32_t nranks, uint32_t *owner,
                           uint32_t *order, uint32_t *counts, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(pipe);
-    if (!o || o->kind != ObjKind::ProgPipe) return -EBADF;
-    auto p = std::static_pointer_cast<ProgPipe>(o);
+    auto p = get_as<ProgPipe>(pipe);
+    if (!p) return -EBADF;
     if (!b || !owner || !order || !counts) return -EFAULT;
     if (nranks == 0 || nranks > 65536 || self_rank >= nranks) return -EINVAL;
     const gf_frames &fr = b->frames;
@@ -8274,9 +8274,7 @@ int gf_pipeline_partition(int pipe, const gf_pipe_batch *b, uint32_t self_rank, 
     PipeDev P{};
     if (p->lb) {
         if ((r = push_map(p->lb->lb4, s)) || (r = push_map(p->lb->lb6, s))) return r;
-        if (p->lb->lb4) P.L.s4 = p->lb->lb4->hdesc();
-        if (p->lb->lb6) P.L.s6 = p->lb->lb6->hdesc();
-        P.L.flags = p->lb->cfg.flags;
+        P.L = lb_dev(*p->lb);
         P.has_lb = 1;
     }
     const uint32_t n = fr.n;
@@ -8943,19 +8941,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     uint32_t strict = 0;
     gf_htab_desc cfg_ct4{}, cfg_ct6{};
     if ((r = ct_limits(ct4m, ct6m, n, 3, s, strict, cfg_ct4, cfg_ct6))) return r;
-    if (pct) {                                          // a family's bit: one of its maps could fill
-        gf_htab_desc d4{}, d6{};
-        for (auto &m : cm.m4) {
-            uint32_t st = 0;
-            if ((r = ct_limits(m, nullptr, n, 3, s, st, d4, d6))) return r;
-            strict |= st;
-        }
-        for (auto &m : cm.m6) {
-            uint32_t st = 0;
-            if ((r = ct_limits(nullptr, m, n, 3, s, st, d4, d6))) return r;
-            strict |= st;
-        }
-    }
+    if (pct && (r = ct_limits_pct(cm, n, 3, s, strict))) return r;   // a family's bit: one of its maps could fill
     auto lxc = node_map(1), tun = node_map(2);
     if ((r = push_map(lxc, s)) || (r = push_map(tun, s))) return r;
     EgWs &ew = eg_ws();
@@ -8974,12 +8960,12 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     // In place (snap_out == the frames) with the check: the flagged pass must leave
     // the frames as they came, so the rewrites go to scratch and are copied at the end
     // (also when tracing: TRACE_FROM_LXC captures the frames as sent).
-    PassArgs ta{};
-    ta.kind = 2;
-    ta.on = event_ring().records && array_traces(a);
-    ta.orig = fr.snap; ta.lxc_id = b->lxc_id;
-    if (ta.on && (r = trace_prepare(n, false, s))) return r;
-    const bool inplace = (check || ta.on) && snap_out == fr.snap;
+    PolicyPass pass;                                    // the deliveries' handle_policy pass, below
+    pass.kind = PassKind::Egress;
+    pass.on = event_ring().records && array_traces(a);
+    pass.orig = fr.snap; pass.lxc_id = b->lxc_id;
+    if (pass.on && (r = trace_prepare(n, false, s))) return r;
+    const bool inplace = (check || pass.on) && snap_out == fr.snap;
     uint8_t *wsnap = inplace ? nullptr : snap_out;
     if (!wsnap) {
         if ((r = grow(ew.snap, (size_t)n * S))) return r;
@@ -8997,11 +8983,11 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     memcpy(E.router6, node.router_ip6, 16); memcpy(E.host6, node.host_ip6, 16);
     if (lxc) {
         E.lxc = lxc->hdesc();
-        if (getenv("GF_XDP_NOSETS") || lxc->addr_set(20, 8192, s, &E.lxset, &E.lxbits, &E.lxzero)) E.lxset = nullptr;
+        front_addr_set(lxc, s, E.lxset, E.lxbits, E.lxzero);
     }
     if (tun) {
         E.tunnel = tun->hdesc();
-        if (getenv("GF_XDP_NOSETS") || tun->addr_set(20, 8192, s, &E.tnset, &E.tnbits, &E.tnzero)) E.tnset = nullptr;
+        front_addr_set(tun, s, E.tnset, E.tnbits, E.tnzero);
     }
     E.snap = wsnap; E.stride = S; E.now = now_sec; E.host_ifindex = host_ifindex();
     E.encap_ifindex = node.encap_ifindex;
@@ -9054,7 +9040,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     }
     E.X.snap = nullptr; E.X.snap_stride = S; E.X.now = now_sec; E.X.gw = node.ipv4_gateway;   // writes: k_eg_groups
     memcpy(E.X.host6, node.host_ip6, 16);
-    if (ta.on) { E.X.tmark = (uint8_t *)trace_ws().mark.p; E.X.tcap = (uint8_t *)trace_ws().px.p; }
+    if (pass.on) { E.X.tmark = (uint8_t *)trace_ws().mark.p; E.X.tcap = (uint8_t *)trace_ws().px.p; }
     if ((r = px_log_begin(n, s, E.X))) return r;
     unsigned long long *sink = (unsigned long long *)stats_sink();
     // With the check, the front counts into a scratch block folded into the sink
@@ -9109,26 +9095,22 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     // the device has the schedule and the groups to run while the host waits for the
     // check's verdict and enqueues the rest of the call behind them
     {
-        uint32_t grid = resident_blocks(8), need = (n + BLOCK - 1) / BLOCK;
-        if (grid > need) grid = need;
+        const uint32_t grid = std::min(resident_blocks(8), (n + BLOCK - 1) / BLOCK);
         ProfScope ps("k_eg_groups", s);
-        if (pct) {
-            hipLaunchKernelGGL((k_eg_groups<4, true>), dim3(grid), dim3(BLOCK), BLOCK * eg_row_bytes(S), s, E,
-                               (uint32_t *)w.sched.p, (const uint2 *)w.order.p, (const uint32_t *)w.perm.p,
-                               (const EgRec *)ew.erec.p, out, (gf_rec *)ew.rec2.p, (uint32_t *)ew.key2.p, nullptr, sink);
-            hipLaunchKernelGGL((k_eg_groups<6, true>), dim3(grid), dim3(BLOCK), 16, s, E, (uint32_t *)w.sched.p,
-                               (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const EgRec *)ew.erec.p, out,
-                               (gf_rec *)ew.rec2.p, (uint32_t *)ew.key2.p, nullptr, sink);
-        } else {
-            hipLaunchKernelGGL(k_eg_groups<4>, dim3(grid), dim3(BLOCK), BLOCK * eg_row_bytes(S), s, E,
-                               (uint32_t *)w.sched.p, (const uint2 *)w.order.p, (const uint32_t *)w.perm.p,
-                               (const EgRec *)ew.erec.p, out, (gf_rec *)ew.rec2.p, (uint32_t *)ew.key2.p,
-                               ct4m ? (uint32_t *)ct4m->d_count.p : nullptr, sink);
-            hipLaunchKernelGGL(k_eg_groups<6>, dim3(grid), dim3(BLOCK), 16, s, E, (uint32_t *)w.sched.p,
-                               (const uint2 *)w.order.p, (const uint32_t *)w.perm.p, (const EgRec *)ew.erec.p, out,
-                               (gf_rec *)ew.rec2.p, (uint32_t *)ew.key2.p, ct6m ? (uint32_t *)ct6m->d_count.p : nullptr,
-                               sink);
-        }
+        // one launch per family: IPv4 stages one header row per lane in LDS (eg_row_bytes of the snap
+        // stride), IPv6 none; the count word is the family's CT map's, null with per-endpoint maps
+        // (pct: each packet's change goes to its own program's map)
+        auto launch = [&](auto k4, auto k6) {
+            auto go = [&](auto kern, size_t lds, const std::shared_ptr<Map> &ct) {
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, s, E, (uint32_t *)w.sched.p, (const uint2 *)w.order.p,
+                                   (const uint32_t *)w.perm.p, (const EgRec *)ew.erec.p, out, (gf_rec *)ew.rec2.p,
+                                   (uint32_t *)ew.key2.p, ct ? (uint32_t *)ct->d_count.p : nullptr, sink);
+            };
+            go(k4, BLOCK * eg_row_bytes(S), ct4m);
+            go(k6, 16, ct6m);
+        };
+        if (pct) launch(k_eg_groups<4, true>, k_eg_groups<6, true>);
+        else launch(k_eg_groups<4>, k_eg_groups<6>);
         if ((r = hip_ok(hipGetLastError(), "k_eg_groups"))) return r;
     }
     uint32_t hz = 0, hz_first = 0;
@@ -9171,7 +9153,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     // keys by exchanging the buffers (the workspace's old ones are the next call's
     // pass-2 buffers), not by copying n records; a fallen-back run takes the pair
     // keys on the device (k_eg_seq_keys' rule, *cflag)
-    auto pack = [&](const uint16_t *, gf_rec *, uint32_t *) -> int {
+    pass.pack = [&](const uint16_t *, gf_rec *, uint32_t *) -> int {
         Workspace &w = ws();
         std::swap(w.rec.p, ew.rec2.p); std::swap(w.rec.bytes, ew.rec2.bytes);
         std::swap(w.keys.p, ew.key2.p); std::swap(w.keys.bytes, ew.key2.bytes);
@@ -9182,10 +9164,15 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
         }
         return 0;
     };
-    if (conn) { ta.rlog = E.rlog; ta.rlog_n = d_rn; ta.rlog_off = E.cflag; ta.rs = E.rs; }
-    if ((r = ingress_run(a, &c2, now_sec, nullptr, s, pack, (uint8_t *)out, fr.len, wsnap, S, wsnap, lru && !conn, true,
-                         false, &ta)))
-        return r;
+    if (conn) { pass.rlog = E.rlog; pass.rlog_n = d_rn; pass.rlog_off = E.cflag; pass.rs = E.rs; }
+    pass.pout = (uint8_t *)out;
+    pass.ev_len = fr.len;
+    pass.ev_snap = wsnap;
+    pass.ev_stride = S;
+    pass.wsnap = wsnap;
+    pass.lru = lru && !conn;                            // (with connection groups: after the related entries, below)
+    pass.px_keep = true;                                // the from-container pass' redirects are in the log
+    if ((r = ingress_run(a, &c2, now_sec, s, pass))) return r;
     if (conn && E.rs.slot) {                           // both passes' related entries: each key's last writer
         ProfScope ps("k_ctlog_apply", s);
         // the deliveries' records are the workspace's now (the pack swap above)
@@ -9304,9 +9291,8 @@ static int egress_runs(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
 extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t now_sec, gf_egress_out *out,
                                       uint8_t *snap_out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(array);
-    if (!o || o->kind != ObjKind::PolicyArray) return -EBADF;
-    auto a = std::static_pointer_cast<PolicyArray>(o);
+    auto a = get_as<PolicyArray>(array);
+    if (!a) return -EBADF;
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
     if (fr.n == 0) return 0;

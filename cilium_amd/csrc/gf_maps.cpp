@@ -194,7 +194,7 @@ static uint64_t pow2ceil64(uint64_t x) {
 
 // ------------------------------------------------------------------ Map
 Map::Map(uint32_t t, uint32_t k, uint32_t v, uint32_t m, uint32_t f)
-    : Obj(ObjKind::Map), type(t), ksz(k), vsz(v), max_entries(m), flags(f),
+    : Obj(KIND), type(t), ksz(k), vsz(v), max_entries(m), flags(f),
       lpm(LpmKeyLess{k > 4 ? k - 4 : 0}) {
     if (!is_lpm()) {
         // LRU maps: a fixed slot array of 4 x max_entries (CT-shaped ones take theirs below), whose
@@ -870,11 +870,6 @@ std::shared_ptr<Obj> get_obj(int h) {
     auto it = r.handles.find(h);
     return it == r.handles.end() ? nullptr : it->second;
 }
-std::shared_ptr<Map> get_map(int h) {
-    auto o = get_obj(h);
-    if (!o || o->kind != ObjKind::Map) return nullptr;
-    return std::static_pointer_cast<Map>(o);
-}
 int new_handle(std::shared_ptr<Obj> o) {
     std::lock_guard<std::mutex> g(reg_lock());
     auto &r = reg();
@@ -1122,7 +1117,7 @@ int gf_node_config(const gf_node_cfg *cfg) {
     if (cfg->lxc_map) {
         lxc = get_map(cfg->lxc_map);
         if (!lxc) return -EBADF;
-        if (lxc->ksz != 20 || lxc->vsz != 112 || lxc->is_lpm()) return -EINVAL;
+        if (!lxc_map_ok(*lxc)) return -EINVAL;
     }
     if (cfg->tunnel_map) {
         tun = get_map(cfg->tunnel_map);

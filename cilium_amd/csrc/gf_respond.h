@@ -338,9 +338,8 @@ int gf_respond_load(const gf_respond_cfg *cfg) {
     auto p = std::make_shared<ProgRespond>();
     p->cfg = *cfg;
     if (cfg->policy_array) {
-        auto a = get_obj(cfg->policy_array);
-        if (!a || a->kind != ObjKind::PolicyArray) return -EBADF;
-        p->policy = std::static_pointer_cast<PolicyArray>(a);
+        p->policy = get_as<PolicyArray>(cfg->policy_array);
+        if (!p->policy) return -EBADF;
     }
     return new_handle(p);
 }
@@ -348,9 +347,8 @@ int gf_respond_load(const gf_respond_cfg *cfg) {
 int gf_respond(int resp, const gf_respond_batch *b, gf_respond_out *out, uint8_t *snap_out, void *stream) {
     // prog_lock: the node config and the array's slots do not change under the call
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(resp);
-    if (!o || o->kind != ObjKind::ProgRespond) return -EBADF;
-    auto p = std::static_pointer_cast<ProgRespond>(o);
+    auto p = get_as<ProgRespond>(resp);
+    if (!p) return -EBADF;
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
     if (fr.n == 0) return 0;

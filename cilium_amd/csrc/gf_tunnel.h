@@ -365,11 +365,6 @@ int tun_opts_check(const uint8_t *opt, uint32_t stride) {
     if (stride < 4 || stride > 64 || stride % 4 || ((uintptr_t)opt & 3u)) return -EINVAL;
     return 0;
 }
-std::shared_ptr<ProgTunnel> tun_get(int tun) {
-    auto o = get_obj(tun);
-    if (!o || o->kind != ObjKind::ProgTunnel) return nullptr;
-    return std::static_pointer_cast<ProgTunnel>(o);
-}
 }  // namespace
 
 extern "C" {
@@ -388,7 +383,7 @@ int gf_tunnel_load(const gf_tunnel_cfg *cfg) {
 int gf_tunnel_encap(int tun, const gf_tunnel_tx *b, uint8_t *out, uint32_t out_stride, uint32_t *out_len,
                     uint8_t *status, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = tun_get(tun);
+    auto p = get_as<ProgTunnel>(tun);
     if (!p) return -EBADF;
     if (!b) return -EFAULT;
     const gf_frames &fr = b->frames;
@@ -442,7 +437,7 @@ int gf_tunnel_select(const void *records, uint32_t rec_kind, uint32_t n, uint8_t
 
 int gf_tunnel_decap(int tun, const gf_frames *outer, const gf_tunnel_rx_out *out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = tun_get(tun);
+    auto p = get_as<ProgTunnel>(tun);
     if (!p) return -EBADF;
     if (!outer || !out) return -EFAULT;
     const gf_frames &fr = *outer;

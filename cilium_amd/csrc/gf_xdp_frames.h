@@ -221,9 +221,8 @@ extern "C" {
 
 int gf_xdp_filter_frames(int prog, const gf_frames *frames, const gf_xdp_frames_out *out, void *stream) {
     std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto o = get_obj(prog);
-    if (!o || o->kind != ObjKind::ProgXdp) return -EBADF;
-    auto p = std::static_pointer_cast<ProgXdp>(o);
+    auto p = get_as<ProgXdp>(prog);
+    if (!p) return -EBADF;
     if (!frames || !out || !out->counts) return -EFAULT;
     const gf_frames &fr = *frames;
     const uint32_t n = fr.n;
