@@ -674,8 +674,9 @@ def fuzz(seed=1, n_packets=20000, n_batches=3, stride=128, ct_max=100000, ct6_ma
     ICMP, deletes, proxies, rev-NAT, weird IHL, truncation and IPv6
     extension-header chains all occur.  Used by the parity tests (a small
     ct_max / ct6_max makes the LRU CT maps overflow and exercises eviction).
-    n_ep: the number of endpoints (>= 12; the default's scenarios are fixed: the
-    golden records), their flag sets repeating after the first 16."""
+    n_ep: the number of endpoints (the default's scenarios are fixed: the golden
+    records), their flag sets repeating after the first 16; cilium_lxc holds the
+    first 12 of them."""
     rng = np.random.default_rng(seed)
     sc = Scenario(f"fuzz{seed}", now=5000)
     ep4 = (ip4("10.1.0.1") + np.arange(n_ep)).astype(np.uint32)
@@ -712,8 +713,10 @@ def fuzz(seed=1, n_packets=20000, n_batches=3, stride=128, ct_max=100000, ct6_ma
     sc.add_map(MapSpec("v6_dyn", LPM, 20, 1, 1024, NO_PREALLOC, k, v))
     k, v = dedup(lpm6_keys(np.full(3, 128), rem6[10:13]), np.ones((3, 1), np.uint8))
     sc.add_map(MapSpec("v6_fix", HASH, 20, 1, 1024, NO_PREALLOC, k, v))
-    lk = np.concatenate([endpoint_keys4(ep4[:12]), endpoint_keys6(ep6[:12])])
-    lv = endpoint_infos(np.arange(24) + 10, np.full(24, 256), np.concatenate([lxc_id[:12], lxc_id[:12]]), np.zeros(24))
+    nl = min(12, n_ep)
+    lk = np.concatenate([endpoint_keys4(ep4[:nl]), endpoint_keys6(ep6[:nl])])
+    lv = endpoint_infos(np.arange(2 * nl) + 10, np.full(2 * nl, 256), np.concatenate([lxc_id[:nl], lxc_id[:nl]]),
+                        np.zeros(2 * nl))
     sc.add_map(MapSpec("cilium_lxc", HASH, 20, 112, 65535, 0, lk, lv))
     sc.xdp = {"cidr4_hmap": "v4_fix", "cidr4_lmap": "v4_dyn", "cidr6_hmap": "v6_fix", "cidr6_lmap": "v6_dyn",
               "lxc_map": "cilium_lxc"}

@@ -1382,6 +1382,22 @@ void o_ingress_batch(const o_prog_array *a, const o_batch *b, uint32_t now, o_in
     plog_free(plog);
 }
 
+/* o_ingress_batch with the frames handle_policy leaves (rev-NAT, the proxy redirect's
+ * rewrites and MAC stores): snap_out starts as a copy of the batch's frames and is the
+ * skb each packet runs on; a packet's proxy-map update is applied right after it. */
+void o_ingress_batch_frames(const o_prog_array *a, const o_batch *b, uint32_t now, o_ingress_out *out,
+                            uint8_t *snap_out) {
+    memcpy(snap_out, b->snap, (size_t)b->n * b->snap_stride);
+    o_batch b2 = *b;
+    b2.snap = snap_out;
+    plog_t plog = plog_new(b->n);
+    for (uint32_t i = 0; i < b->n; i++) {
+        handle_policy(a, &b2, i, now, &out[i], plog, snap_out);
+        if (plog.mark[i]) proxy_apply_one(&b2, plog.log, out, snap_out, i);
+    }
+    plog_free(plog);
+}
+
 /* ------------------------------------------------------------------ */
 /* multi-threaded drivers (CPU baseline)                               */
 /* ------------------------------------------------------------------ */

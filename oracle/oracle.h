@@ -5,8 +5,10 @@
  * and bench.py's cpu_baseline leg may load it.  The product (libgpuflow)
  * never links or calls it.
  *
- * Written line-by-line from the reference text (read, never compiled):
- * each function cites the file:line it restates.  Kernel map semantics
+ * Written line-by-line from the reference text: each function cites the
+ * file:line it restates.  handle_policy and bpf_lb's from-netdev are also
+ * compared with the reference programs executed as host code
+ * (oracle/refdiff.py, oracle/REFDIFF.md, tests/test_ref_diff.py).  Kernel map semantics
  * (htab exact match over key_size bytes, LPM trie longest-prefix match,
  * E2BIG/ENOSPC at max_entries) follow the Linux kernel's published
  * behaviour (kernel/bpf/hashtab.c, kernel/bpf/lpm_trie.c), which are not in
@@ -130,6 +132,9 @@ void o_set_node(const o_node_cfg *node);
 /* Sequential handle_policy over the batch in order (one CPU). */
 void o_ingress_batch(const o_prog_array *a, const o_batch *b, uint32_t now_sec,
                      o_ingress_out *out);
+/* The same, also returning each frame as handle_policy left it (snap_out: n * snap_stride). */
+void o_ingress_batch_frames(const o_prog_array *a, const o_batch *b, uint32_t now_sec,
+                            o_ingress_out *out, uint8_t *snap_out);
 /* T threads, packets partitioned by unordered address pair (RSS-like);
  * CT maps must have been created with shards == T. */
 void o_ingress_batch_mt(const o_prog_array *a, const o_batch *b, uint32_t now_sec,

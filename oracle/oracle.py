@@ -87,6 +87,7 @@ _s("o_prog_array_destroy", None, VP)
 _s("o_prog_array_set", None, VP, C.c_uint32, C.POINTER(o_lxc_cfg))
 _s("o_set_node", None, C.POINTER(o_node_cfg))
 _s("o_ingress_batch", None, VP, C.POINTER(o_batch), C.c_uint32, VP)
+_s("o_ingress_batch_frames", None, VP, C.POINTER(o_batch), C.c_uint32, VP, VP)
 _s("o_ingress_batch_mt", None, VP, C.POINTER(o_batch), C.c_uint32, VP, C.c_uint32)
 _s("o_pipeline_batch_mt", None, C.POINTER(o_pipeline_cfg), C.POINTER(o_batch), C.c_uint32, VP, VP, VP, C.c_uint32, VP)
 _s("o_ingress_events", None, VP, C.POINTER(o_batch), VP, VP)
@@ -268,6 +269,14 @@ def ingress(prog_array, b, now, threads=1):
     else:
         lib.o_ingress_batch(prog_array, C.byref(b), now, out.ctypes.data)
     return out
+
+
+def ingress_frames(prog_array, b, now):
+    """o_ingress_batch_frames: returns (records ING_OUT, frames as handle_policy left them)."""
+    out = np.zeros(b.n, ING_OUT)
+    snap = np.zeros((b.n, b.snap_stride), np.uint8)
+    lib.o_ingress_batch_frames(prog_array, C.byref(b), now, out.ctypes.data, snap.ctypes.data)
+    return out, snap
 
 
 def pipeline(cfg, b, now, threads=1, events=False):

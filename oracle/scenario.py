@@ -123,6 +123,13 @@ class OracleDP:
             self.lru_after_call(now)
         return out
 
+    def ingress_frames(self, pk, now):
+        """ingress() that also returns the frames as handle_policy left them."""
+        O.lib.o_set_node(C.byref(self._node))
+        out, snap = O.ingress_frames(self.arr, self.batch(pk), now)
+        self.lru_after_call(now)
+        return out, snap
+
     def ingress_events(self, pk, out):
         return O.ingress_events(self.arr, self.batch(pk), out)
 
