@@ -218,6 +218,24 @@ GF_EVD_F_PACKED, GF_EVD_F_RESET = 1 << 0, 1 << 1
 GF_EVD_MAX_WINDOW = 1 << 24
 
 
+class gf_forward_ifindex(C.Structure):
+    _fields_ = [("ifindex_lo", C.c_uint16), ("queue", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class gf_forward_cfg(C.Structure):
+    _fields_ = [("n_queues", C.c_uint32), ("stack_queue", C.c_uint8), ("responder_queue", C.c_uint8),
+                ("default_queue", C.c_uint8), ("pad", C.c_uint8), ("n_ifindex", C.c_uint32),
+                ("ifindex", C.POINTER(gf_forward_ifindex))]
+
+
+class gf_forward_out(C.Structure):
+    _fields_ = [("snap", C.c_void_p), ("len", C.c_void_p), ("index", C.c_void_p), ("max_out", C.c_uint32),
+                ("qoff", C.c_void_p), ("counts", C.c_void_p)]
+
+
+GF_FWD_MAX_QUEUES, GF_FWD_DROP, GF_REC_LB = 64, 0xff, 3
+
+
 def _sig(name, res, *args):
     f = getattr(lib, name)
     f.restype = res
@@ -275,6 +293,9 @@ _sig("gf_tunnel_decap", C.c_int, C.c_int, C.POINTER(gf_frames), C.POINTER(gf_tun
 _sig("gf_event_filter_load", C.c_int, C.POINTER(gf_event_filter_cfg))
 _sig("gf_event_drain", C.c_int, C.c_int, C.POINTER(gf_event_ring), C.c_uint32, C.c_uint32, C.c_uint32, VP, C.c_uint64,
      VP, VP, VP)
+_sig("gf_forward_load", C.c_int, C.POINTER(gf_forward_cfg))
+_sig("gf_forward_queues", C.c_int, C.c_int, VP, C.c_uint32, C.c_uint32, VP, VP)
+_sig("gf_forward_frames", C.c_int, C.POINTER(gf_frames), VP, C.c_uint32, C.POINTER(gf_forward_out), VP)
 _sig("gf_ct_gc", C.c_int, C.c_int, C.c_uint32, VP)
 _sig("gf_ct_gc_maps", C.c_int, C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), VP)
 _sig("gf_proxy_gc", C.c_int, C.c_int, C.c_uint32, VP)
@@ -309,7 +330,7 @@ EXPORTED = [
     "gf_obj_close", "gf_obj_unpin", "gf_now_sec", "gf_parse_frames", "gf_xdp_prog_load",
     "gf_xdp_classify", "gf_xdp_filter_frames", "gf_lb_prog_load", "gf_lb_classify", "gf_lb_prog_set_dstmac", "gf_lb_classify_frames", "gf_lxc_prog_load",
     "gf_policy_array_create", "gf_policy_array_update", "gf_node_config",
-    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_tunnel_load", "gf_tunnel_encap", "gf_tunnel_select", "gf_tunnel_decap", "gf_event_filter_load", "gf_event_drain", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
+    "gf_policy_ingress_classify", "gf_policy_ingress_classify_batches", "gf_pipeline_load", "gf_pipeline_classify", "gf_pipeline_classify_tunnel", "gf_pipeline_partition", "gf_overlay_load", "gf_overlay_classify", "gf_overlay_classify_opts", "gf_lxc_egress_tunnel_meta", "gf_host_load", "gf_host_classify", "gf_respond_load", "gf_respond", "gf_respond_calls", "gf_tunnel_load", "gf_tunnel_encap", "gf_tunnel_select", "gf_tunnel_decap", "gf_event_filter_load", "gf_event_drain", "gf_forward_load", "gf_forward_queues", "gf_forward_frames", "gf_lxc_egress_classify", "gf_ct_gc", "gf_ct_gc_maps", "gf_proxy_gc", "gf_proxy_cleanup_port", "gf_ct_evict_log", "gf_set_event_ring", "gf_set_stats_sink", "gf_prof_enable", "gf_prof_read", "gf_dev_alloc", "gf_dev_free",
     "gf_memcpy_h2d", "gf_memcpy_d2h", "gf_stream_sync", "gf_device_count", "gf_version", "gf_build_id",
 ]
 

@@ -102,7 +102,7 @@ struct HTab {
     void rehash(uint64_t new_nslots);
 };
 
-enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond, ProgTunnel, EventFilter };
+enum class ObjKind { Map, ProgXdp, ProgLb, ProgLxc, PolicyArray, ProgPipe, ProgOverlay, ProgHost, ProgRespond, ProgTunnel, EventFilter, Forward };
 
 struct Obj {
     ObjKind kind;
@@ -304,6 +304,16 @@ struct EventFilter : Obj {         // cilium monitor's --type / --from / --to / 
     DevBuf d_bits;                 // their device copy, uploaded by the first drain
     std::mutex mu;
     EventFilter() : Obj(KIND) {}
+};
+
+struct Forward : Obj {             // the verdict -> output queue rule (gf_forward.h)
+    static constexpr ObjKind KIND = ObjKind::Forward;
+    uint32_t n_queues = 0;
+    uint8_t stack_queue = 0, responder_queue = 0, default_queue = 0;
+    std::vector<uint8_t> table;    // ifindex_lo -> queue, 65536 bytes (default_queue without an entry)
+    DevBuf d_table;                // its device copy, uploaded by the first gf_forward_queues
+    std::mutex mu;
+    Forward() : Obj(KIND) {}
 };
 
 // Element ceiling of an insert through the map API (single updates, the host

@@ -9333,3 +9333,6 @@ extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t
 
 // ---- the prefilter over raw frames: k_xdpf_*, gf_xdp_filter_frames ----
 #include "gf_xdp_frames.h"
+
+// ---- forwarding the verdicts: k_fwd_*, gf_forward_queues, gf_forward_frames ----
+#include "gf_forward.h"

@@ -21,7 +21,8 @@ from ._lib import (lib, gf_frames, gf_pkt_cols, gf_pkt_cols_out, gf_xdp_cfg, gf_
                    gf_overlay_batch, gf_tunnel_opts, gf_host_cfg, gf_host_batch, gf_respond_cfg, gf_respond_batch,
                    gf_tunnel_cfg, gf_tunnel_tx, gf_tunnel_rx_out, GF_TUN_GENEVE,
                    gf_event_ring, gf_event_drain_out, GF_EVENT_RECORD, GF_EVD_F_PACKED, GF_EVD_F_RESET, GF_EVD_MAX_WINDOW,
-                   GF_CALL_ICMP6_TIME_EXCEEDED, GF_REC_EGRESS, GF_REC_PIPELINE)
+                   GF_CALL_ICMP6_TIME_EXCEEDED, GF_REC_EGRESS, GF_REC_PIPELINE,
+                   gf_forward_cfg, gf_forward_ifindex, gf_forward_out, GF_FWD_DROP)
 
 LB_OUT = np.dtype([("action", "u1"), ("reason", "u1"), ("slave", "<u2"), ("new_dport", "<u2"),
                    ("rev_nat", "<u2"), ("new_daddr4", "<u4")])
@@ -151,6 +152,7 @@ class Datapath:
         self.fd = {}
         self._resp = {}
         self._tun = {}
+        self._fwd = []
         self.ring = None
         for name, m in sc.maps.items():
             fd = bpf.CreateMap(m.type, m.ksz, m.vsz, m.max_entries, m.flags)
@@ -521,6 +523,45 @@ class Datapath:
         _check(lib.gf_tunnel_decap(tun, C.byref(fr), C.byref(ro), _stream()), "gf_tunnel_decap")
         return r
 
+    # ---- forwarding the verdicts: the frames of a classified batch, packed per output queue ----
+    def forward_load(self, n_queues, stack_queue=GF_FWD_DROP, responder_queue=GF_FWD_DROP, default_queue=GF_FWD_DROP,
+                     ifindex=()):
+        """gf_forward_load: a forward handle (closed with the datapath).  ifindex: (ifindex_lo, queue)
+        pairs, a later pair for the same ifindex_lo winning; a queue is < n_queues or GF_FWD_DROP."""
+        ent = (gf_forward_ifindex * max(len(ifindex), 1))(*[gf_forward_ifindex(i, q, 0) for i, q in ifindex])
+        cfg = gf_forward_cfg(n_queues, stack_queue, responder_queue, default_queue, 0, len(ifindex),
+                             ent if len(ifindex) else None)
+        h = _check(lib.gf_forward_load(C.byref(cfg)), "gf_forward_load")
+        self._fwd.append(h)
+        return h
+
+    def forward_queues(self, fwd, kind, records):
+        """gf_forward_queues: the queue column [n] u8 of a classify call's records (kind GF_REC_EGRESS,
+        GF_REC_PIPELINE or GF_REC_LB), by the rule table of include/gpuflow.h."""
+        torch = _torch()
+        n = records.shape[0]
+        queue = torch.empty(n, dtype=torch.uint8, device=records.device)
+        _check(lib.gf_forward_queues(fwd, _ptr(records), kind, n, _ptr(queue), _stream()), "gf_forward_queues")
+        return queue
+
+    def forward_frames(self, frames, len, queue, n_queues, max_out=None, index=True):
+        """gf_forward_frames over frames [n,stride] u8, len [n] i32 and a queue column [n] u8 (device
+        tensors).  Returns (frames [max_out,stride] u8, len [max_out] i32, index [max_out] i32 or
+        None, qoff [n_queues + 1] i32, counts [4] i32 = forwarded, not forwarded, written, invalid
+        queue bytes), all on the device: queue q owns rows [qoff[q], qoff[q + 1]), in arrival
+        order; the first counts[2] rows are defined.  max_out: the capacity in rows (default n)."""
+        torch = _torch()
+        n = frames.shape[0]
+        cap = n if max_out is None else max_out
+        e = lambda dt, *shape: torch.empty(shape, dtype=dt, device=frames.device)
+        snap, ln = e(torch.uint8, cap, frames.shape[1]), e(torch.int32, cap)
+        ix = e(torch.int32, cap) if index else None
+        qoff, counts = e(torch.int32, n_queues + 1), e(torch.int32, 4)
+        fr = gf_frames(n, frames.shape[1], _ptr(frames), _ptr(len))
+        o = gf_forward_out(_ptr(snap), _ptr(ln), _ptr(ix), cap, _ptr(qoff), _ptr(counts))
+        _check(lib.gf_forward_frames(C.byref(fr), _ptr(queue), n_queues, C.byref(o), _stream()), "gf_forward_frames")
+        return snap, ln, ix, qoff, counts
+
     # ---- the event ring and its drain (cilium monitor's filters on the device) ----
     def set_event_ring(self, capacity, device="cuda"):
         """gf_set_event_ring over a fresh ring of `capacity` slots (None: no ring).  The ring is
@@ -594,7 +635,7 @@ class Datapath:
     def close(self):
         """Close the program objects, then the maps (a program holds its maps, so
         their device tables are released once both are closed)."""
-        progs = list(self._resp.values()) + list(self._tun) + [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
+        progs = list(self._resp.values()) + list(self._tun) + list(self._fwd) + [self.host, self.ovl, self.pipe, self.policy_array, self.lb_prog, self.xdp_prog] + list(getattr(self, "lxc_progs", []))
         for h in [h for h in progs if h] + list(self.fd.values()):
             try:
                 bpf.ObjClose(h)
@@ -604,6 +645,7 @@ class Datapath:
         self.lxc_progs = []
         self._resp = {}
         self._tun = {}
+        self._fwd = []
         self.fd = {}
         if getattr(self, "ring", None) is not None:
             self.set_event_ring(None)

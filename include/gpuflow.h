@@ -42,6 +42,8 @@
  *     gf_parse_frames            <- the skb_load_bytes()/revalidate_data() header
  *                                   accesses of those programs (bpf/lib/common.h:67-87,
  *                                   bpf/lib/ipv4.h:45-48, bpf/lib/ipv6.h:61-98)
+ *     gf_forward_queues / gf_forward_frames <- what the verdict does to the skb: SHOT frees it, OK hands
+ *                                   it to the stack, redirect(ifindex) queues it on that device
  *
  * Host/device contract: map updates go to the host shadow and are pushed to
  * the HBM replica at the next classify call (batch boundary; a documented
@@ -1263,6 +1265,81 @@ typedef struct gf_event_drain_out {  /* DEVICE, written by the call */
  * overlapping the ring's records, records not 4-byte aligned); -E2BIG (max_n > GF_EVD_MAX_WINDOW). */
 int gf_event_drain(int filter, const gf_event_ring *ring, uint32_t first, uint32_t max_n, uint32_t flags,
                    uint8_t *out, uint64_t out_bytes, uint32_t *out_off, gf_event_drain_out *res, void *stream);
+
+/* ---- forwarding the verdicts: gf_forward_load, gf_forward_queues, gf_forward_frames ----
+ * The last step of a chain of frame operators.  In the reference a verdict moves the packet:
+ * TC_ACT_SHOT frees the skb, TC_ACT_OK hands it to the stack, redirect(ifindex) puts it on that
+ * device's queue.  Here: a stable multi-way partition of the classified frames into at most
+ * GF_FWD_MAX_QUEUES output queues, in two calls, so that the partition works for any queue column
+ * and not only for the record kinds below.
+ *
+ * gf_forward_queues: queue[i] from record i of a classify call, the first row that matches:
+ *   1  GF_REC_PIPELINE with stage == GF_STAGE_XDP (the action byte is XDP_DROP)   GF_FWD_DROP
+ *   2  a responder tail call is pending (gf_respond_calls yields a call other than
+ *      GF_CALL_NONE; no frame byte is read for this):
+ *        GF_REC_EGRESS    eg_flags & (GF_EG_F_ARP | GF_EG_F_RESPONDER | GF_EG_F_ICMP6_TE)
+ *        GF_REC_PIPELINE  flags & (GF_PIPE_F_ICMP6_TE | GF_PIPE_F_RESPONDER)         responder_queue
+ *   3  action TC_ACT_SHOT                                                         GF_FWD_DROP
+ *   4  action TC_ACT_OK                                                           stack_queue
+ *   5  action TC_ACT_REDIRECT: the queue of the entry for the record's ifindex_lo, or
+ *      default_queue without one; GF_REC_LB, whose record carries no ifindex (bpf_lb has one
+ *      target, LB_REDIRECT): always default_queue
+ *   6  any other action byte                                                      GF_FWD_DROP
+ * GF_REC_LB records have no stage and no flags: rows 3 to 6 only. */
+#define GF_FWD_MAX_QUEUES 64
+#define GF_FWD_DROP       0xffu      /* queue value: the frame is not forwarded */
+#define GF_REC_LB         3          /* gf_lb_out (12 B), next to GF_REC_EGRESS / GF_REC_PIPELINE */
+typedef struct gf_forward_ifindex { uint16_t ifindex_lo; uint8_t queue; uint8_t pad; } gf_forward_ifindex;
+typedef struct gf_forward_cfg {
+    uint32_t n_queues;          /* 1..GF_FWD_MAX_QUEUES */
+    uint8_t  stack_queue;       /* TC_ACT_OK frames; a queue < n_queues or GF_FWD_DROP */
+    uint8_t  responder_queue;   /* frames with a responder tail call pending (for gf_respond) */
+    uint8_t  default_queue;     /* REDIRECT to an ifindex without an entry; every REDIRECT of GF_REC_LB */
+    uint8_t  pad;
+    uint32_t n_ifindex;
+    const gf_forward_ifindex *ifindex;   /* HOST; a later entry for the same ifindex_lo wins */
+} gf_forward_cfg;
+/* A forward handle (gf_obj_close frees it); the entries are copied.  On the device the rule is a
+ * 65536-byte ifindex_lo -> queue table (default_queue where there is no entry), built here and
+ * uploaded by the handle's first gf_forward_queues (the one call that waits for a copy).
+ * -EFAULT (NULL cfg; n_ifindex > 0 with a NULL ifindex), -EINVAL (n_queues outside
+ * 1..GF_FWD_MAX_QUEUES; stack_queue, responder_queue, default_queue or an entry's queue that is
+ * neither < n_queues nor GF_FWD_DROP). */
+int gf_forward_load(const gf_forward_cfg *cfg);
+/* queue[i] (DEVICE, n bytes) from the records (DEVICE) of a classify call, by the table above.
+ * One launch (k_fwd_queues).  -EBADF (not a forward handle), -EFAULT (n > 0 with NULL records or
+ * queue), -EINVAL (rec_kind), -E2BIG (n > 2^30); n == 0 returns 0. */
+int gf_forward_queues(int fwd, const void *records, uint32_t rec_kind, uint32_t n, uint8_t *queue, void *stream);
+
+/* Row i of `frames` is forwarded iff queue[i] < n_queues; GF_FWD_DROP and every other byte
+ * >= n_queues are not (the latter are counted in counts[3]).  The forwarded rows are packed
+ * queue-major, in arrival order inside a queue (the partition is stable): queue q owns the output
+ * rows [qoff[q], qoff[q + 1]).  A packed row is the whole input row (snap_stride bytes, verbatim,
+ * the bytes past len included); len[r] is its wire length and index[r] its batch index i, the
+ * handle for the record and any side column the caller carries along.  qoff and counts[0] come
+ * from the full counts whatever max_out is; output row r is written iff r < max_out, and nothing
+ * at or past row counts[2] is written in snap, len or index: the call is asynchronous and cannot
+ * fail late.  There is no in-place mode.  The call takes no handle and no map locks, and touches
+ * neither the event ring nor the stats sink.  Three launches after the queue column (k_fwd_count,
+ * k_fwd_scan, k_fwd_scatter); no block waits for another.  Rows move in 16-byte pieces when
+ * frames->snap, out->snap and snap_stride are multiples of 16, in 4-byte pieces when of 4, else
+ * byte by byte.
+ * Errors, all before anything is launched or written: -EFAULT (NULL frames, queue, out, qoff or
+ * counts; n > 0 with a NULL frames->snap or frames->len; out->snap without out->len), -EINVAL
+ * (n_queues outside 1..GF_FWD_MAX_QUEUES; n > 0 with snap_stride outside 14..256; out->snap NULL
+ * with out->len or out->index; an output buffer that overlaps frames->snap, frames->len or queue),
+ * -E2BIG (n > 2^30).  n == 0 returns 0 and writes qoff and counts (zeros). */
+typedef struct gf_forward_out {
+    uint8_t  *snap;     /* DEVICE, max_out * snap_stride: whole rows, queue-major, arrival order inside a queue; may be NULL */
+    uint32_t *len;      /* DEVICE, max_out; NULL only with snap NULL */
+    uint32_t *index;    /* DEVICE, max_out: batch index of each packed row; may be NULL */
+    uint32_t  max_out;
+    uint32_t *qoff;     /* DEVICE, n_queues + 1 words, required: queue q owns rows [qoff[q], qoff[q+1]) */
+    uint32_t *counts;   /* DEVICE, 4 words, required: [0] forwarded = qoff[n_queues], [1] not forwarded,
+                           [2] rows written = min([0], max_out) (0 with snap NULL), [3] queue bytes >= n_queues other than GF_FWD_DROP */
+} gf_forward_out;
+int gf_forward_frames(const gf_frames *frames, const uint8_t *queue, uint32_t n_queues,
+                      const gf_forward_out *out, void *stream);
 
 #ifdef __cplusplus
 }
