@@ -1,14 +1,16 @@
 // gf_kernels.hip — gfx950 kernels of libgpuflow and the program/classify C ABI.
 //
-//   k_parse     raw frames -> SoA header columns   (skb_load_bytes rules)
-//   k_xdp       bpf/bpf_xdp.c:88-184               one packet per lane
-//   k_lb        bpf/bpf_lb.c:58-212 + lib/lb.h      one packet per lane
-//   k_ing_pack  columns -> 32-B records + flow-group key (unordered addr pair)
-//   (rocPRIM stable radix sort of (group, index) + exclusive scan)
-//   k_bucket_*  bucket-size histogram + count-descending bucket order
-//   k_ing_level bpf/bpf_lxc.c:745-1024 handle_policy, level-synchronous: launch k
-//               runs the k-th packet of every flow-group bucket (CT ordering rule)
-//   k_ing_tail  the remaining ranks of the few deepest buckets, sequentially
+//   k_parse      raw frames -> SoA header columns   (skb_load_bytes rules)
+//   k_xdp        bpf/bpf_xdp.c:88-184               one packet per lane
+//   k_lb         bpf/bpf_lb.c:58-212 + lib/lb.h      one packet per lane
+//   k_ing_pack   columns -> 32-B records + flow-group key (unordered addr pair)
+//   (rocPRIM stable radix sort of (key, index); k_run_*: one bucket per run of equal keys)
+//   k_bucket_*   bucket-size histogram + count-descending bucket order
+//   k_ing_groups bpf/bpf_lxc.c:745-1024 handle_policy: a lane takes a flow-group bucket
+//                off its family's queue and runs the bucket's packets in batch order
+//                (CT ordering rule)
+//   k_*_front    the frame entry points in front of it (pipeline, from-overlay, from-host)
+//   k_eg_*       bpf/bpf_lxc.c:427-738 from-container
 #include "gf_internal.h"
 #include "gf_device.h"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -32,10 +34,7 @@ using namespace gf;
 using namespace gfd;
 
 #define BLOCK 256
-#ifndef GF_DIAG
-#define GF_DIAG 0      // diagnostic ablations (tools/diag.sh); 0 in the product build
-#endif
-// Tuning knobs of the flow-group kernel (tools/variants.sh sweeps them).
+// Tuning knobs of the flow-group kernel (tools/variant.sh builds a library per setting).
 // The bucket key (gf_key_cfg, gf_common.h: family bit + bits-1 bits of the group
 // hash; GF_KEY_BITS forces a width, GF_SORT_RADIX sets the digit).
 // The key of every packet the handle_policy pass skips (a pipeline packet that
@@ -54,12 +53,6 @@ __device__ __forceinline__ uint32_t gf_key_live(uint32_t h, const gf_key_cfg &K)
 #ifndef GF_ING_MINW6
 #define GF_ING_MINW6 3      // IPv6 buckets: the lane state (RelCache<10>) keeps the block at 3 per CU by LDS
 #endif
-#ifndef GF_ING_BINS_WAVE
-#define GF_ING_BINS_WAVE 0  // k_ing_groups: reason / action bins aggregated over the active lanes (no effect: 2.728 ms both)
-#endif
-#ifndef GF_PERM_VEC
-#define GF_PERM_VEC 1       // k_ing_groups: the bucket's indices read four at a time (16-B loads; 2.625 -> 2.615 ms)
-#endif
 #ifndef GF_EG_MINW
 #define GF_EG_MINW 3        // k_eg_groups: min waves per SIMD (4 spills: 1.65 vs 1.60 ms, egress leg)
 #endif
@@ -72,12 +65,6 @@ __device__ __forceinline__ uint32_t gf_key_live(uint32_t h, const gf_key_cfg &K)
 #ifndef GF_FRONT_MINW
 #define GF_FRONT_MINW 8     // k_pipe_front: __launch_bounds__ min waves per SIMD (64 VGPRs: 1.294 vs 1.410 ms, config 4)
 #endif
-#ifndef GF_EG_DYN
-#define GF_EG_DYN 1         // k_eg_front: LDS rows sized by the snap stride (64-B snaps: half the LDS; 0.586 vs 0.622 ms)
-#endif
-#ifndef GF_EG_LEAN
-#define GF_EG_LEAN 1        // egress: the deferred-entry sets sized by the logged count, empty-family and no-IPv6 blocks skipped
-#endif
 #define GF_RUN_ITEMS 4096u  // keys per tile of the run-start / single-bucket count-scan-write passes
 // Buckets per lane per queue grab once a wave reaches the single-packet buckets
 // (the lists are longest first, so from there on every bucket is one packet): one
@@ -89,12 +76,6 @@ __device__ __forceinline__ uint32_t gf_key_live(uint32_t h, const gf_key_cfg &K)
 #endif
 #ifndef GF_GRAB_EG
 #define GF_GRAB_EG 2        // k_eg_groups
-#endif
-#ifndef GF_SINGLE_ORDER
-#define GF_SINGLE_ORDER 1   // egress passes: single-packet buckets scheduled in packet-index order
-#endif
-#ifndef GF_REC_NT
-#define GF_REC_NT 0         // k_ing_groups: packet records read with nontemporal loads
 #endif
 #ifndef GF_CT_COOP6
 #define GF_CT_COOP6 1       // the same for CT6 (168 VGPRs: fits the 3 waves the LDS allows; 1.242 vs 1.252 ms)
@@ -444,16 +425,12 @@ __device__ __forceinline__ bool lxc_has6(const gf_htab_desc &lxc, const uint32_t
 // xdp_start -> check_filters -> check_v4 / check_v6 (bpf/bpf_xdp.c:97-184) for
 // packet i; ab accumulates the algorithmic bytes.  The three lookups (the LPM
 // trie, the /32 or /128 hash, the cilium_lxc endpoint) have no side effects, so
-// GF_XDP_PRE can load the hash probes' home lines before the trie walk (all in
-// flight together; the verdict still combines them in the reference's order).
-// Measured on config 1 (r2): 0.080 ms with both lines preloaded, 0.076 with the
-// prefix hash only, 0.075 with none — k_xdp is bound by the request rate of its
-// L2-resident tables, not by the latency of the chain, so the default issues
-// each probe only when the reference would.
+// the hash probes' home lines could be loaded before the trie walk (all in flight
+// together).  Measured on config 1 (r2): 0.080 ms with both lines preloaded, 0.076
+// with the prefix hash only, 0.075 with none — k_xdp is bound by the request rate
+// of its L2-resident tables, not by the latency of the chain, so each probe is
+// issued only when the reference would.
 #define GF_XDP_U 2
-#ifndef GF_XDP_PRE
-#define GF_XDP_PRE 0      // home lines loaded before the trie walk: 0 none, 1 the prefix hash, 2 + cilium_lxc
-#endif
 template <class A>
 __device__ __forceinline__ uint8_t xdp_verdict(const XdpDev &x, const A &a, uint32_t len, uint32_t et, uint32_t &ab) {
     if (len < 14) return XDP_DROP_;
@@ -463,9 +440,7 @@ __device__ __forceinline__ uint8_t xdp_verdict(const XdpDev &x, const A &a, uint
         const uint32_t kw[2] = {32u, sa};
         const uint32_t lk[5] = {a.daddr4(), 0, 0, 0, 1u};     // endpoint_key {ip4, pad.., family=1}
         ProbeLine<20, GF_XDP_U> ll;
-        if (GF_XDP_PRE >= 2) ll.load(x.lxc, key_hash<20>(lk));
         ProbeLine<8, GF_XDP_U> hl;
-        if (GF_XDP_PRE >= 1 && x.has_h4) hl.load(x.h4, key_hash<8>(kw));
         bool drop = false;
         ab += 10;
         if (x.has_h4) {
@@ -485,7 +460,7 @@ __device__ __forceinline__ uint8_t xdp_verdict(const XdpDev &x, const A &a, uint
                 ab += 9;
                 if (x.h4set) drop = aset_has(x.h4set, x.h4bits, x.h4zero, sa);
                 else {
-                    if (GF_XDP_PRE < 1) hl.load(x.h4, key_hash<8>(kw));
+                    hl.load(x.h4, key_hash<8>(kw));
                     drop = probe2<8, GF_XDP_U, 0>(x.h4, kw, kw, hl, false).f >= 0;
                 }
             }
@@ -493,7 +468,7 @@ __device__ __forceinline__ uint8_t xdp_verdict(const XdpDev &x, const A &a, uint
         if (drop) return XDP_DROP_;
         ab += 20;
         if (x.lxset) return aset_has(x.lxset, x.lxbits, x.lxzero, lk[0]) ? XDP_PASS_ : XDP_DROP_;
-        if (GF_XDP_PRE < 2) ll.load(x.lxc, key_hash<20>(lk));
+        ll.load(x.lxc, key_hash<20>(lk));
         return probe2<20, GF_XDP_U, 0>(x.lxc, lk, lk, ll, false).f >= 0 ? XDP_PASS_ : XDP_DROP_;
     }
     if (et == 0x86DD) {
@@ -504,9 +479,7 @@ __device__ __forceinline__ uint8_t xdp_verdict(const XdpDev &x, const A &a, uint
         const uint4 d = a.daddr6();
         const uint32_t lk[5] = {d.x, d.y, d.z, d.w, 2u};
         ProbeLine<20, GF_XDP_U> ll;
-        if (GF_XDP_PRE >= 2) ll.load(x.lxc, key_hash<20>(lk));
         ProbeLine<20, GF_XDP_U> hl;
-        if (GF_XDP_PRE >= 1 && x.has_h6) hl.load(x.h6, key_hash<20>(kw));
         bool drop = false;
         ab += 34;
         if (x.has_h6) {
@@ -514,13 +487,13 @@ __device__ __forceinline__ uint8_t xdp_verdict(const XdpDev &x, const A &a, uint
             if (trie_lookup<4>(x.l6, sw)) drop = true;
             else {
                 ab += 21;
-                if (GF_XDP_PRE < 1) hl.load(x.h6, key_hash<20>(kw));
+                hl.load(x.h6, key_hash<20>(kw));
                 drop = probe2<20, GF_XDP_U, 0>(x.h6, kw, kw, hl, false).f >= 0;
             }
         }
         if (drop) return XDP_DROP_;
         ab += 20;
-        if (GF_XDP_PRE < 2) ll.load(x.lxc, key_hash<20>(lk));
+        ll.load(x.lxc, key_hash<20>(lk));
         return probe2<20, GF_XDP_U, 0>(x.lxc, lk, lk, ll, false).f >= 0 ? XDP_PASS_ : XDP_DROP_;
     }
     return XDP_PASS_;
@@ -808,12 +781,6 @@ __global__ __launch_bounds__(BLOCK) void k_lb(gf_pkt_cols c, LbDev L, gf_lb_out 
 #define GF_LXC_DEV_HAS_CT4 (1u << 30)
 #define GF_LXC_DEV_HAS_CT6 (1u << 31)
 
-#ifndef GF_POUT_WO
-#define GF_POUT_WO 1        // gf_pipeline_classify: complete the records without reading them (IngCtx::pout_wo)
-#endif
-#ifndef GF_EG_RSET
-#define GF_EG_RSET 1        // egress connection groups: related entries through RelSet (0: the r5 write log)
-#endif
 // The ICMP-related entries of an egress connection-group run: the
 // only CT keys two connections of one address pair share, written (BPF_ANY) by every
 // new connection of the pair in both passes and read by nothing in the run.  Only the
@@ -847,7 +814,7 @@ struct IngCtx {
     uint8_t *tmark, *tcap;     // trace notifications: per-packet GF_TR_* marks, 128-B captures (null: off)
     uint32_t *rlog, *rlog_n;   // egress connection groups: ct_create4's related entries logged (null: written)
     const uint32_t *rlog_off;  // device word: nonzero = the run fell back to pair groups (entries written inline)
-    RelSet rs;                 // GF_EG_RSET: the related entries' set (rlog non-null: in use)
+    RelSet rs;                 // the related entries' set (rlog non-null: in use; slot null: the log itself)
 };
 
 // ---- handle_policy's own header writes (kept out of line: cold paths of the
@@ -1022,12 +989,9 @@ struct Ep {
         sl = s;
         const gf_lxc_dev *c = X.cfgs + (s - 1);
         flags = gload<uint32_t>(&c->flags);
-        // (diagnosis GF_DIAG & 32: every endpoint reads program 0's policy map — one
-        // L2-resident table instead of 256 in the MALL; verdicts differ)
-        const gf_lxc_dev *pc = (GF_DIAG & 32) ? X.cfgs : c;
-        pol = gload<uint8_t *>(&pc->policy.slots);
+        pol = gload<uint8_t *>(&c->policy.slots);
         pol_side = gload<uint8_t *>(&c->policy.vals);
-        pol_mask = (uint32_t)gload<uint64_t>(&pc->policy.mask);
+        pol_mask = (uint32_t)gload<uint64_t>(&c->policy.mask);
     }
     __device__ __forceinline__ const gf_lxc_dev *cfg(const IngCtx &X) const { return X.cfgs + (sl - 1); }
     __device__ __forceinline__ gf_htab_desc pdesc() const {
@@ -1055,7 +1019,7 @@ __device__ __forceinline__ gf_htab_desc ing_ct(const IngCtx &X, const Ep &ep) {
 // (conntrack.h:563-577) is the same key for the whole group: a lane keeps
 // where it lives.  Only this lane changes keys of its group; a delete by the
 // lane clears the cache.
-// IPv4 (GF_REL_DEFER): the lane also keeps the entry's last hot-part rewrite
+// IPv4: the lane also keeps the entry's last hot-part rewrite
 // pending instead of storing each one — the value of an ingress create's related
 // entry is fixed by now (per launch), the protocol's timeout and the packet's
 // length — in the spare high bits of the cached key's last word (bits 16-31: the
@@ -1063,9 +1027,6 @@ __device__ __forceinline__ gf_htab_desc ing_ct(const IngCtx &X, const Ep &ep) {
 // ICMP packet of the lane: only ct_lookup4's related probe matches the key),
 // before the cache moves to another entry and at the end of the launch.  A group
 // creating 4 flows a step then writes its related entry once instead of 4 times.
-#ifndef GF_REL_DEFER
-#define GF_REL_DEFER 1
-#endif
 template <int TW>
 struct RelCache {
     uint32_t k[TW];
@@ -1238,7 +1199,7 @@ __device__ __forceinline__ int ct_create(const gf_htab_desc &d, uint32_t *t, uin
     v[1] = (fl | F_SEEN_NON_SYN) | (rev_nat << 16);
     if constexpr (KSZ == 14) if (rlog) {                // connection groups: applied after the run, in order
         GF_WR(WR_RLOG);
-        if (GF_EG_RSET && rs->slot) {
+        if (rs->slot) {
             rset_put(*rs, it[0], it[1], (it[NHW] >> 8) & 1u, order);
             return 0;
         }
@@ -1255,7 +1216,7 @@ __device__ __forceinline__ int ct_create(const gf_htab_desc &d, uint32_t *t, uin
     for (int k = 0; k < TW; k++) same &= ((k == TW - 1 ? rc.k[k] & 0x7fffu : rc.k[k]) == it[k]);
     if (same) {                                         // BPF_ANY over the entry this lane wrote
         if (d.vin == 16 && rc.sec == src_sec) {         // cold part (rx hi, tx, src_sec_id) unchanged
-            if constexpr (TW == 4 && GF_REL_DEFER) {    // (rev_nat is 0 on the ingress path)
+            if constexpr (TW == 4) {                    // (rev_nat is 0 on the ingress path)
                 rc.k[3] = (rc.k[3] & 0x7fffu) | (((len << 1) | (nh == 6 ? 1u : 0u)) << 15);
             } else {
                 store_words<4>(d.slots + (uint64_t)rc.slot * d.slot_size + d.voff, v);
@@ -1309,11 +1270,7 @@ __device__ __forceinline__ int l4_proxy_lookup(const gf_lxc_dev *c, uint32_t nh,
 // configurations, whose lanes rarely share an entry (config 2 2.535 -> 2.565 ms,
 // config 4 1.902 -> 1.957: profiles/r5q_*.json).  Counter sums commute: the final
 // values are the reference's.
-#ifndef GF_POL_WAVE
-#define GF_POL_WAVE 1
-#endif
 __device__ __forceinline__ void pol_count_add(uint8_t *c, uint32_t pk, uint32_t by, bool wave) {
-#if GF_POL_WAVE
   if (wave) {
     const uint64_t act = __ballot(1);
     const uint32_t lane = threadIdx.x & 63u, lead = (uint32_t)__ffsll((unsigned long long)act) - 1u;
@@ -1333,7 +1290,6 @@ __device__ __forceinline__ void pol_count_add(uint8_t *c, uint32_t pk, uint32_t 
         return;
     }
   }
-#endif
     gadd64(c, (unsigned long long)pk);
     gadd64(c + 8, (unsigned long long)by);
 }
@@ -1347,10 +1303,8 @@ struct PolAcc {
     __device__ __forceinline__ void flush_one(const IngCtx &X, int j) {
         if (sl[j]) {
             uint8_t *side = gload<uint8_t *>(&X.cfgs[sl[j] - 1].policy.vals);
-            // (GF_DIAG & 32: the slot came from program 0's map; counted in the endpoint's own array)
-            const uint32_t fj = (GF_DIAG & 32) ? f[j] & (uint32_t)gload<uint64_t>(&X.cfgs[sl[j] - 1].policy.mask) : f[j];
-            uint8_t *c = side + (uint64_t)fj * GF_POL_SIDE;
-            if (!(GF_DIAG & 256)) pol_count_add(c, pk[j], by[j], X.pol_wave != 0);   // (GF_DIAG & 256: ablation)
+            uint8_t *c = side + (uint64_t)f[j] * GF_POL_SIDE;
+            pol_count_add(c, pk[j], by[j], X.pol_wave != 0);
             GF_WR(WR_POLCNT); GF_WR(WR_POLCNT);
         }
         sl[j] = 0; pk[j] = 0; by[j] = 0;
@@ -1536,12 +1490,6 @@ __device__ __forceinline__ int policy_ingress(const IngCtx &X, Ep &ep, PolLine &
                                               const uint32_t *cidr_addr, uint32_t &ab, PolAcc &acc, PolMemo<N> &m,
                                               uint32_t *dk = nullptr) {
     const uint32_t pk = dport | (proto << 16), sip = v6 ? 0u : cidr_addr[0];
-#if GF_DIAG & 16
-    // diagnosis (ceiling of any policy-map staging): no policy-map read, the counter
-    // update kept on a pseudo-random slot of the endpoint's map; verdicts differ
-    policy_count(X, ep, (int64_t)((identity * 0x9E3779B1u + pk) & ep.pol_mask), len, acc);
-    return TC_OK;
-#endif
     const bool memo_ok = !v6 || identity >= 256;
     const int j = memo_ok ? m.find(ep.sl, identity, pk, sip) : -1;
     if (j >= 0) {
@@ -1697,7 +1645,7 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
     PolLine pl;
     const bool pre = r.src_identity &&
                      (flags & (GF_LXC_F_POLICY_INGRESS | GF_LXC_F_DROP_ALL)) == GF_LXC_F_POLICY_INGRESS &&
-                     !pm.hit(ep.sl, r.src_identity, (t[2] >> 16) | (nh << 16), r.saddr) && !(GF_DIAG & (4 | 16));
+                     !pm.hit(ep.sl, r.src_identity, (t[2] >> 16) | (nh << 16), r.saddr);
     if (pre) pl.load(ep.pdesc(), pol_home(r.src_identity, 0u, 0u));
     bool acct = (flags & GF_LXC_F_CT_ACCOUNTING) != 0;
     CtState st{0, 0, 0};
@@ -1735,8 +1683,7 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
         dl->w[0] |= dk | ((dk & GF_DBG_L4_PROXY) ? (uint32_t)verdict << 16 : 0u);
         dl->w[4] = t[2] & 0xffffu;
     } else {
-        verdict = (GF_DIAG & 4) ? 0 : policy_ingress(X, ep, pl, pre, r.src_identity, t[2] & 0xffffu, nh, len, false,
-                                                     &orig_sip, ab, acc, pm);
+        verdict = policy_ingress(X, ep, pl, pre, r.src_identity, t[2] & 0xffffu, nh, len, false, &orig_sip, ab, acc, pm);
     }
     if (ret != CT_REPLY && ret != CT_RELATED && verdict < 0) {
         if (ret == CT_ESTABLISHED) {
@@ -1747,7 +1694,7 @@ __device__ int ipv4_policy(const IngCtx &X, Ep &ep, const gf_rec &r, uint32_t i,
         return D_POLICY;
     }
     if (r.cls & 4) verdict = 0;                         // skip_proxy
-    if (ret == CT_NEW && !(GF_DIAG & 8)) {
+    if (ret == CT_NEW) {
         if constexpr (DBG) dl->w[0] |= GF_DBG_CREATED;
         ret = ct_create<14, 4, GF_CT4_U>(ct, t, 0u, r.src_identity, len, X.now, X.strict & 1, pr, added, rc, ab,
                                          RL ? rlog : nullptr, X.rlog_n, 2u * i + 1u, &X.rs);
@@ -2074,39 +2021,24 @@ __device__ __forceinline__ void ing_one(const IngCtx &X, uint32_t i, const gf_re
         *reinterpret_cast<uint16_t *>(q + 8) = o.ifindex_lo;
     } else if (X.pout) {                                // complete the pipeline / egress record
         uint8_t *q = X.pout + 24 * (size_t)i;
-        // (GF_DIAG & 128: ablation, the record's kept bytes not read — records wrong)
-        uint2 a = (GF_DIAG & 128) ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2 *>(q);
-        uint2 b = (GF_DIAG & 128) ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2 *>(q + 8);
+        uint2 a = *reinterpret_cast<const uint2 *>(q);
+        uint2 b = *reinterpret_cast<const uint2 *>(q + 8);
         a.x = (a.x & 0xffu) | ((uint32_t)o.action << 8) | ((uint32_t)o.reason << 16) | ((uint32_t)o.ct_ret << 24);
         a.y = ((a.y & 0xffu) | o.flags) | (a.y & 0xff00u) | ((uint32_t)o.proxy_port << 16);
         b.x = (b.x & 0xffff0000u) | o.ifindex_lo;
         *reinterpret_cast<uint2 *>(q) = a;
         *reinterpret_cast<uint2 *>(q + 8) = b;
-    } else if (!(GF_DIAG & 1)) {
+    } else {
         out[i] = o;
         GF_WR(WR_OUT);
     }
-    if (stats && !(GF_DIAG & 2)) {
-#if GF_ING_BINS_WAVE
-        st.bins_wave(true, o.reason, o.action);         // the active lanes' bins, one LDS atomic per distinct pair
-#else
+    if (stats) {
         st.add(o.reason); st.add(256 + o.action);
-#endif
         ln.sc.add(r.len, ab, o.ct_ret & 3u, st);
     }
 }
 
-__device__ __forceinline__ gf_rec ld_rec(const gf_rec *rec, uint32_t i) {
-    if constexpr (GF_REC_NT) {
-        const uint4 a = gload_nt16(rec + i), b = gload_nt16(reinterpret_cast<const uint8_t *>(rec + i) + 16);
-        gf_rec r;
-        __builtin_memcpy(&r, &a, 16);
-        __builtin_memcpy(reinterpret_cast<uint8_t *>(&r) + 16, &b, 16);
-        return r;
-    } else {
-        return rec[i];
-    }
-}
+__device__ __forceinline__ gf_rec ld_rec(const gf_rec *rec, uint32_t i) { return rec[i]; }
 __device__ __forceinline__ void flush_added(const IngCtx &X, uint32_t fam_bit, int added, uint32_t *ct_count,
                                             uint32_t *lds_added) {
     if (X.strict & fam_bit) return;
@@ -2115,42 +2047,28 @@ __device__ __forceinline__ void flush_added(const IngCtx &X, uint32_t fam_bit, i
     if (threadIdx.x == 0 && *lds_added && ct_count) atomicAdd(ct_count, *lds_added);
 }
 
-// Bucket lists: family (IPv4 / IPv6 CT path) x endpoint class.  A bucket's class
-// is its first packet's endpoint slot mod GF_NCLS (a scheduling hint only: a bucket
-// is still one lane's, whole); the lanes of workgroup b start on the lists of class
-// b mod GF_NCLS — the XCD the workgroup runs on, dispatch being round-robin over the
-// 8 XCDs — and move to the other classes' lists when theirs is drained, so that an
-// XCD's L2 would hold the policy maps of its class of endpoints only.  Measured with
-// 8 classes: k_ing_groups 2.90 vs 2.40 ms on config 2; the cause is not pinned
-// down.  (Not CT locality: a CT home line is placed by gf_key_hash / GF_HASH_CT
-// over the whole tuple, ports included, which is unrelated to the bucket key's
-// gf_pair_hash4, so neighbours in key order never shared CT pages.)  One class
-// (the plain longest-first list) stays.
-#ifndef GF_NCLS
-#define GF_NCLS 1u
-#endif
-#define GF_NL (2u * GF_NCLS)
-// Schedule words (device): hist[GF_NL][GF_LCAP+1] | base[..] | cursor[..] | nruns |
-// queue[GF_NL] | nfam[2] | lcnt[GF_NL] | lstart[GF_NL] (lists in order: family 0's
-// classes, then family 1's; each list by bucket size, descending).
+// Bucket lists: one per family (IPv4 / IPv6 CT path), each the plain longest-first
+// list.  (Lists per family x endpoint class, a workgroup starting on the class of
+// the XCD it runs on so that an XCD's L2 would hold the policy maps of its class of
+// endpoints only, measured slower with 8 classes: k_ing_groups 2.90 vs 2.40 ms on
+// config 2, DESIGN.md.)
+// Schedule words (device): hist[GF_FAMS][GF_LCAP+1] | base[..] | cursor[..] | nruns |
+// queue[GF_FAMS] | nfam[GF_FAMS] | lcnt[GF_FAMS] | lstart[GF_FAMS] (family 0's list,
+// then family 1's; each list by bucket size, descending).
+#define GF_FAMS 2u            // families = lists: IPv4, IPv6
 #define GF_LCAP 1024u
 #define GF_SCHED_HIST(p) (p)
-#define GF_SCHED_BASE(p) ((p) + GF_NL * (GF_LCAP + 1))
-#define GF_SCHED_CURSOR(p) ((p) + 2 * GF_NL * (GF_LCAP + 1))
-#define GF_SCHED_NRUNS(p) ((p) + 3 * GF_NL * (GF_LCAP + 1))
+#define GF_SCHED_BASE(p) ((p) + GF_FAMS * (GF_LCAP + 1))
+#define GF_SCHED_CURSOR(p) ((p) + 2 * GF_FAMS * (GF_LCAP + 1))
+#define GF_SCHED_NRUNS(p) ((p) + 3 * GF_FAMS * (GF_LCAP + 1))
 #define GF_SCHED_QUEUE(p) (GF_SCHED_NRUNS(p) + 1)
-#define GF_SCHED_NFAM(p) (GF_SCHED_QUEUE(p) + GF_NL)
-#define GF_SCHED_LCNT(p) (GF_SCHED_NFAM(p) + 2)
-#define GF_SCHED_LSTART(p) (GF_SCHED_LCNT(p) + GF_NL)
-#define GF_SCHED_WORDS (3 * GF_NL * (GF_LCAP + 1) + 1 + GF_NL + 2 + 2 * GF_NL)
-#define GF_SCHED_HBYTES (GF_NL * (GF_LCAP + 1) * 4)    // the block-local bins of k_bucket_hist / order (dynamic LDS)
-// The list of a bucket: family from its key, class from its first packet's record.
-__device__ __forceinline__ uint32_t sched_list(uint32_t key, const gf_rec *rec, const uint32_t *perm, uint32_t b,
-                                               const gf_key_cfg &K) {
-    const uint32_t f = key >> (K.bits - 1);
-    const uint32_t x = rec ? (uint32_t)rec[perm[b]].ep % GF_NCLS : 0u;
-    return f * GF_NCLS + x;
-}
+#define GF_SCHED_NFAM(p) (GF_SCHED_QUEUE(p) + GF_FAMS)
+#define GF_SCHED_LCNT(p) (GF_SCHED_NFAM(p) + GF_FAMS)
+#define GF_SCHED_LSTART(p) (GF_SCHED_LCNT(p) + GF_FAMS)
+#define GF_SCHED_WORDS (3 * GF_FAMS * (GF_LCAP + 1) + 1 + 4 * GF_FAMS)
+#define GF_SCHED_HBYTES (GF_FAMS * (GF_LCAP + 1) * 4)    // the block-local bins of k_bucket_hist / order (dynamic LDS)
+// The list of a bucket: the family bit of its key.
+__device__ __forceinline__ uint32_t sched_list(uint32_t key, const gf_key_cfg &K) { return key >> (K.bits - 1); }
 
 // GRAB: buckets per lane per queue grab in the single-packet tail (GF_GRAB_ING for the
 // egress deliveries' pass, whose buckets are mostly single packets; 1 elsewhere,
@@ -2174,12 +2092,13 @@ __global__ __launch_bounds__(BLOCK, FAM == 6 ? GF_ING_MINW6 : GF_ING_MINW) void 
     Lane<FAM> &ln = lanes[threadIdx.x];
     ln.init();
     uint32_t *const rlog = RL && X.rlog && !(X.rlog_off && *X.rlog_off) ? X.rlog : nullptr;
-    const uint32_t x0 = blockIdx.x % GF_NCLS;           // this workgroup's XCD class first
-    for (uint32_t xi = 0; xi < GF_NCLS; xi++) {
-    const uint32_t L = F * GF_NCLS + (x0 + xi) % GF_NCLS;
-    uint32_t *queue = GF_SCHED_QUEUE(sched) + L;
-    const uint32_t nb = lcnt[L];
-    const uint2 *lorder = order + lstart[L];
+    // (the family's one list.  The one-trip loop is what is left of a loop over several lists:
+    // without it the compiler allocates this kernel's registers differently, which would have
+    // to be measured again.)
+    for (uint32_t li = 0; li < 1u; li++) {
+    uint32_t *queue = GF_SCHED_QUEUE(sched) + F;
+    const uint32_t nb = lcnt[F];
+    const uint2 *lorder = order + lstart[F];
     // the wave's grab: [base, base + 64 * left) of the list, one 64-bucket round at a
     // time (wave-uniform values); grab = buckets per lane of the next grab
     uint32_t grab = 1, gbase = 0, left = 0;
@@ -2212,23 +2131,17 @@ __global__ __launch_bounds__(BLOCK, FAM == 6 ? GF_ING_MINW6 : GF_ING_MINW) void 
         uint32_t inx = c > 1 ? perm[b + 1] : 0u;
         gf_rec r = ld_rec(rec, i);
         lane_rel_drop<FAM, PCT>(X, ln);                  // a new bucket: new flow groups
-#if GF_PERM_VEC
-        uint4 pw = make_uint4(0, 0, 0, 0);               // perm[j & ~3 .. +3], j = b + k + 2
+        uint4 pw = make_uint4(0, 0, 0, 0);               // perm[j & ~3 .. +3], j = b + k + 2: 16-B loads
         if (c > 2) pw = *reinterpret_cast<const uint4 *>(perm + ((b + 2) & ~3u));
-#endif
         for (uint32_t k = 0; k < c; k++) {
             // the next record and the index after it are in flight while packet k runs
             uint32_t in2 = 0;
-#if GF_PERM_VEC
             if (k + 2 < c) {
                 const uint32_t j = b + k + 2;
                 if (!(j & 3u) && k) pw = *reinterpret_cast<const uint4 *>(perm + j);
                 const uint32_t q = j & 3u;
                 in2 = q == 0 ? pw.x : q == 1 ? pw.y : q == 2 ? pw.z : pw.w;
             }
-#else
-            if (k + 2 < c) in2 = perm[b + k + 2];
-#endif
             ing_one<FAM, PCT, RL>(X, i, r, out, st, stats != nullptr, ln, rlog);
             i = inx; inx = in2;
             if (k + 1 < c) r = ld_rec(rec, i);
@@ -2264,11 +2177,10 @@ __global__ __launch_bounds__(BLOCK, FAM == 6 ? GF_ING_MINW6 : GF_ING_MINW) void 
     __shared__ Lane<FAM> lanes[BLOCK];
     Lane<FAM> &ln = lanes[threadIdx.x];
     ln.init();
-    for (uint32_t xi = 0; xi < GF_NCLS; xi++) {
-        const uint32_t L = F * GF_NCLS + (blockIdx.x % GF_NCLS + xi) % GF_NCLS;
-        uint32_t *queue = GF_SCHED_QUEUE(sched) + L;
-        const uint32_t nb = GF_SCHED_LCNT(sched)[L];
-        const uint2 *lorder = order + GF_SCHED_LSTART(sched)[L];
+    for (uint32_t li = 0; li < 1u; li++) {              // (one trip, as in k_ing_groups)
+        uint32_t *queue = GF_SCHED_QUEUE(sched) + F;
+        const uint32_t nb = GF_SCHED_LCNT(sched)[F];
+        const uint2 *lorder = order + GF_SCHED_LSTART(sched)[F];
         for (;;) {
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(queue, 64u);
@@ -2464,17 +2376,18 @@ __global__ __launch_bounds__(BLOCK) void k_ing_noct(IngCtx X, uint32_t n, uint32
     }
 }
 
-#define GF_LCAP 1024u
 // Bucket-size histogram per family (the top bit of the bucket's sorted key, K.fam):
 // block-local LDS bins, one global add per non-empty bin.
 #define GF_SCHED_ITEMS 4096
 // off[q]: the start of run q in the sorted keys (nruns of them); its length is
-// the distance to the next start (or to n).
+// the distance to the next start (or to n).  (rec and perm are not read: they gave a
+// bucket's endpoint class when the lists had classes, and stay in the two signatures so
+// that the kernels compile to the code they were measured as.)
 __global__ __launch_bounds__(BLOCK) void k_bucket_hist(uint32_t n, const uint32_t *off, const uint32_t *skeys,
                                                        const gf_rec *rec, const uint32_t *perm, uint32_t *sched,
                                                        gf_key_cfg K) {
     extern __shared__ uint32_t h[];                     // GF_SCHED_HBYTES
-    for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x) h[k] = 0;
+    for (uint32_t k = threadIdx.x; k < GF_FAMS * (GF_LCAP + 1); k += blockDim.x) h[k] = 0;
     __syncthreads();
     uint32_t nq = *GF_SCHED_NRUNS(sched);
     uint32_t b0 = blockIdx.x * GF_SCHED_ITEMS;
@@ -2482,11 +2395,11 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_hist(uint32_t n, const uint32_
         const uint32_t key = skeys[off[q]];
         uint32_t c = (q + 1 < nq ? off[q + 1] : n) - off[q];
         if (c && key != gf_key_skip(K))
-            atomicAdd(&h[sched_list(key, rec, perm, off[q], K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
+            atomicAdd(&h[sched_list(key, K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
     }
     __syncthreads();
     uint32_t *hist = GF_SCHED_HIST(sched);
-    for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x)
+    for (uint32_t k = threadIdx.x; k < GF_FAMS * (GF_LCAP + 1); k += blockDim.x)
         if (h[k]) atomicAdd(&hist[k], h[k]);
 }
 
@@ -2502,7 +2415,7 @@ __global__ __launch_bounds__(GF_LCAP) void k_bucket_base(uint32_t *sched) {
     uint32_t *base = GF_SCHED_BASE(sched), *cursor = GF_SCHED_CURSOR(sched);
     if (k == 0) { tot = 0; GF_SCHED_NFAM(sched)[0] = GF_SCHED_NFAM(sched)[1] = 0; }
     __syncthreads();
-    for (uint32_t l = 0; l < GF_NL; l++) {
+    for (uint32_t l = 0; l < GF_FAMS; l++) {
         const uint32_t *hf = hist + l * (GF_LCAP + 1);
         s[k] = hf[c];
         __syncthreads();
@@ -2520,7 +2433,7 @@ __global__ __launch_bounds__(GF_LCAP) void k_bucket_base(uint32_t *sched) {
         if (k == GF_LCAP - 1) {
             GF_SCHED_LCNT(sched)[l] = s[k];
             GF_SCHED_LSTART(sched)[l] = add;
-            GF_SCHED_NFAM(sched)[l / GF_NCLS] += s[k];
+            GF_SCHED_NFAM(sched)[l] += s[k];
             GF_SCHED_QUEUE(sched)[l] = 0;
             tot = add + s[k];
         }
@@ -2535,7 +2448,7 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_order(uint32_t n, const uint32
                                                         const gf_rec *rec, const uint32_t *perm, uint32_t *sched,
                                                         uint2 *order, uint32_t skip1, gf_key_cfg K) {
     extern __shared__ uint32_t h[];                     // GF_SCHED_HBYTES
-    for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x) h[k] = 0;
+    for (uint32_t k = threadIdx.x; k < GF_FAMS * (GF_LCAP + 1); k += blockDim.x) h[k] = 0;
     __syncthreads();
     uint32_t nq = *GF_SCHED_NRUNS(sched);
     const uint32_t *base = GF_SCHED_BASE(sched);
@@ -2545,21 +2458,21 @@ __global__ __launch_bounds__(BLOCK) void k_bucket_order(uint32_t n, const uint32
         const uint32_t key = skeys[off[q]];
         uint32_t c = (q + 1 < nq ? off[q + 1] : n) - off[q];
         if (c && key != gf_key_skip(K) && !(skip1 && c == 1))
-            atomicAdd(&h[sched_list(key, rec, perm, off[q], K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
+            atomicAdd(&h[sched_list(key, K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u);
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < GF_NL * (GF_LCAP + 1); k += blockDim.x)
+    for (uint32_t k = threadIdx.x; k < GF_FAMS * (GF_LCAP + 1); k += blockDim.x)
         if (h[k]) h[k] = base[k] + atomicAdd(&cursor[k], h[k]);
     __syncthreads();
     for (uint32_t q = b0 + threadIdx.x; q < b0 + GF_SCHED_ITEMS && q < nq; q += blockDim.x) {
         const uint32_t key = skeys[off[q]];
         uint32_t c = (q + 1 < nq ? off[q + 1] : n) - off[q];
         if (c && key != gf_key_skip(K) && !(skip1 && c == 1))
-            order[atomicAdd(&h[sched_list(key, rec, perm, off[q], K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u)] =
+            order[atomicAdd(&h[sched_list(key, K) * (GF_LCAP + 1) + (c < GF_LCAP ? c : GF_LCAP)], 1u)] =
                 make_uint2(off[q], c);
     }
 }
-// Single-packet buckets in packet-index order (GF_SINGLE_ORDER, the egress passes,
+// Single-packet buckets in packet-index order (the egress passes,
 // whose connection groups are mostly one packet a step): the tail of each family's
 // list (bin c = 1) is filled by packet index, so a wave's lanes read neighbouring
 // records, frames and output rows instead of 64 random ones.  k_single_mark writes
@@ -2600,7 +2513,7 @@ __global__ __launch_bounds__(BLOCK) void k_single_write(uint32_t n, const uint32
                                                         const uint32_t *t1, const uint32_t *sched, uint2 *order) {
     __shared__ uint32_t wc[2][BLOCK / 64];
     const uint32_t b0 = blockIdx.x * GF_RUN_ITEMS, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const uint32_t *base = GF_SCHED_BASE(sched);         // bin c = 1 of family f's list (GF_NCLS == 1)
+    const uint32_t *base = GF_SCHED_BASE(sched);         // bin c = 1 of family f's list
     uint32_t p0 = base[0 * (GF_LCAP + 1) + 1] + t0[blockIdx.x], p1 = base[1 * (GF_LCAP + 1) + 1] + t1[blockIdx.x];
     for (uint32_t k = 0; k < GF_RUN_ITEMS / BLOCK; k++) {
         const uint32_t j = b0 + k * BLOCK + threadIdx.x;
@@ -3806,10 +3719,6 @@ __global__ __launch_bounds__(BLOCK) void k_px_gc(gf_htab_desc d, PxGcPred P, con
 // way.  Key bytes of the cleared slots are zeroed.  Every eviction is logged
 // (gf_ct_evict_log: batch number, now, K, the hand's first line, lines passed,
 // entries deleted).
-#ifndef GF_LRU_NT
-#define GF_LRU_NT 0         // the eviction passes' slot loads nontemporal (same-box A/B r6e: the hand 7-12 % slower,
-                            // the next k_ing_groups unchanged: off)
-#endif
 #define GF_LRU_BINS 65536u
 #define GF_LRU_LOGCAP 4096u
 #define GF_LRU_SAMPLE_SHIFT 10
@@ -3887,9 +3796,10 @@ struct LruSlot {
     static constexpr uint32_t SZ = KIND == 2 ? 64u : 32u, SPL = 128u / SZ, KW = KIND == 2 ? 10 : 4;
     uint32_t kw[KW];
     uint32_t st = GF_SLOT_EMPTY, lt = 0, fl = 0;
-    // nontemporal loads: the eviction passes stream GBs of slots per call, which must
-    // not push the policy maps and hot CT lines of the next launch out of L2 / MALL
-    __device__ __forceinline__ static uint4 ld(const uint8_t *p) { return GF_LRU_NT ? gload_nt16(p) : gload<uint4>(p); }
+    // plain loads: the eviction passes stream GBs of slots per call, but nontemporal loads
+    // (to spare the next launch's policy maps and hot CT lines in L2 / MALL) made the hand
+    // 7-12 % slower and left the next k_ing_groups unchanged (same-box A/B, r6e)
+    __device__ __forceinline__ static uint4 ld(const uint8_t *p) { return gload<uint4>(p); }
     __device__ __forceinline__ void load(const gf_htab_desc &d, uint64_t i) {
         const uint8_t *p = d.slots + i * SZ;
         if constexpr (KIND == 2) {
@@ -4839,7 +4749,7 @@ struct EgDev {
     uint32_t *cflag;                    // device word: 1 = pair groups (an IPv4 ICMP packet reaches conntrack)
     uint32_t *keysP, *key2P;            // the pair keys of the front / of the deliveries (fallback)
     uint32_t *rlog, *rlog_n;            // logged related entries {order, key[4], value[12], pad[3]}
-    RelSet rs;                          // GF_EG_RSET: their set instead
+    RelSet rs;                          // their set instead (slot null: the log)
     gf_rec *rec2;                       // the handle_policy pass's records: the front writes every packet's
     uint32_t *key2;                     //   as "not delivered" in batch order, k_eg_groups only the deliveries
 };
@@ -4887,12 +4797,8 @@ struct EgDev {
 // per lane in LDS: one vector load per row instead of a global access per byte.
 #define GF_EG_STAGE 128u
 GF_HD uint32_t eg_stage_bytes(uint32_t S) { return S < GF_EG_STAGE ? S : GF_EG_STAGE; }
-#ifndef GF_EG_GROUPS_DYN
-#define GF_EG_GROUPS_DYN 1  // k_eg_groups: LDS rows sized by the snap stride (0: GF_EG_STAGE-byte rows)
-#endif
-GF_HD uint32_t eg_row_bytes(uint32_t S) {           // k_eg_groups' LDS row
-    return GF_EG_GROUPS_DYN ? (eg_stage_bytes(S) + 15u) & ~15u : GF_EG_STAGE;
-}
+// k_eg_groups' LDS row: sized by the snap stride
+GF_HD uint32_t eg_row_bytes(uint32_t S) { return (eg_stage_bytes(S) + 15u) & ~15u; }
 __device__ __forceinline__ void eg_copy(uint8_t *dst, const uint8_t *src, uint32_t n) {
     if (!(n & 15u) && !(((uintptr_t)src | (uintptr_t)dst) & 15u)) {
         for (uint32_t k = 0; k < n; k += 16) *reinterpret_cast<uint4 *>(dst + k) = *reinterpret_cast<const uint4 *>(src + k);
@@ -5461,7 +5367,7 @@ __device__ __forceinline__ void ct_hit_eg(const gf_htab_desc &d, int64_t f, int 
     }
     st.rev_nat = hot.y >> 16;
     st.loopback = (fl >> 3) & 1u;
-    if (acct && !(GF_DIAG & 64)) {                      // tx_packets += 1, tx_bytes += len (GF_DIAG & 64: ablation)
+    if (acct) {                                         // tx_packets += 1, tx_bytes += len
         uint8_t *base = d.sstride ? ht_side(d, (uint64_t)f) - 16 : e;   // internal value word k at base + 4k
         gstore<unsigned long long>(base + 24, gload<unsigned long long>(base + 24) + 1ull);
         gstore<unsigned long long>(base + 32, gload<unsigned long long>(base + 32) + (unsigned long long)len);
@@ -5648,7 +5554,7 @@ __device__ __forceinline__ int eg_ct_part(const EgDev &E, const EgRec &r, uint32
         }
         uint32_t it[4] = {t[0], t[1], 0u, 1u | ((((t[3] >> 8) & 0xffu) | 2u) << 8)};
         v[1] |= F_SEEN_NON_SYN;
-        if (rlog && GF_EG_RSET && E.rs.slot) {          // the run's set (RelSet), applied after the run
+        if (rlog && E.rs.slot) {                        // the run's set (RelSet), applied after the run
             rset_put(E.rs, it[0], it[1], (it[3] >> 8) & 1u, 2u * i);
         } else if (rlog) {                              // applied after the run, in packet order (the pair's
             uint32_t *lg = E.rlog + (size_t)GF_CTLOG_WORDS * wave_reserve(E.rlog_n);   // other connections
@@ -5958,7 +5864,7 @@ __global__ __launch_bounds__(BLOCK, GF_EG_MINW) void k_eg_groups(EgDev E, uint32
                                                      const EgRec *erec, gf_egress_out *out, gf_rec *rec2, uint32_t *key2,
                                                      uint32_t *ct_count, unsigned long long *stats) {
     if (E.hz && *E.hz) return;                          // hazard: the batch reruns in ordered runs
-    if (GF_EG_LEAN && !GF_SCHED_NFAM(sched)[FAM == 6 ? 1 : 0]) return;   // no bucket of this family (nothing to count)
+    if (!GF_SCHED_NFAM(sched)[FAM == 6 ? 1 : 0]) return;   // no bucket of this family (nothing to count)
     __shared__ uint32_t sl[272];
     __shared__ uint32_t sadd;
     // FAM 4: one LDS row per lane of the staged header bytes, sized by the snap
@@ -5975,10 +5881,9 @@ __global__ __launch_bounds__(BLOCK, GF_EG_MINW) void k_eg_groups(EgDev E, uint32
     const uint32_t K = eg_stage_bytes(E.stride);
     uint8_t *row = reinterpret_cast<uint8_t *>(lds) + (FAM == 6 ? 0 : threadIdx.x * eg_row_bytes(E.stride));
     constexpr int F = FAM == 6 ? 1 : 0;
-    // the from-container pass schedules without records: every bucket is in class 0
-    const uint32_t nb = GF_SCHED_LCNT(sched)[F * GF_NCLS], lane = threadIdx.x & 63u;
-    uint32_t *queue = GF_SCHED_QUEUE(sched) + F * GF_NCLS;
-    order += GF_SCHED_LSTART(sched)[F * GF_NCLS];
+    const uint32_t nb = GF_SCHED_LCNT(sched)[F], lane = threadIdx.x & 63u;
+    uint32_t *queue = GF_SCHED_QUEUE(sched) + F;
+    order += GF_SCHED_LSTART(sched)[F];
     const bool seq = *E.seq != 0;
     const bool rlog = FAM == 4 && E.conn && !seq && !*E.cflag;   // connection groups: related entries logged
     int added = 0;
@@ -6108,7 +6013,7 @@ __device__ __forceinline__ bool ctlog_same(const uint32_t *a, const uint32_t *b)
 // walks zero again — the set is all zero between applies (zeroed once when it is
 // allocated), so no launch of its own clears it.
 __device__ __forceinline__ uint32_t ctlog_mask(uint32_t n, uint32_t cap_mask) {
-    const uint64_t want = GF_EG_LEAN ? 2ull * n : (uint64_t)cap_mask + 1;
+    const uint64_t want = 2ull * n;
     uint32_t t = 1023u;
     while ((uint64_t)t + 1 < want && t < cap_mask) t = t * 2 + 1;
     return t < cap_mask ? t : cap_mask;
@@ -6257,7 +6162,7 @@ void prof_drain() {
 
 struct Workspace {
     DevBuf rec, keys, skeys, perm, tcnt, off, tmp, sched, order;
-    DevBuf sb, st0, st1;               // single-packet buckets in index order (GF_SINGLE_ORDER)
+    DevBuf sb, st0, st1;               // single-packet buckets in index order (the egress passes)
 };
 // GF_HOST_PROF (diagnosis): the host time of a classify call's phases, one line
 // per call on stderr (where a call waits on the device, or spends its launches).
@@ -6754,7 +6659,7 @@ struct PolicyPass {
     bool prepared = false;         // pack + schedule already built in ws() (ingress_prepare)
     uint32_t *rlog = nullptr, *rlog_n = nullptr;   // egress connection groups: the related-entry log (null: written inline)
     const uint32_t *rlog_off = nullptr;            // device word: the run fell back to pair groups (the log is not used)
-    RelSet rs{};                   // GF_EG_RSET: the related entries' set (rlog then only marks it in use)
+    RelSet rs{};                   // the related entries' set (rlog then only marks it in use)
     bool on = false;               // frames / egress: this call traces (a ring is set and a program / the netdev traces)
     uint32_t nd_trace = 0, nd_ifindex = 0;   // pipeline / overlay: 0, or the front's observation point | its final
                                    // stage << 8 (EvSrc::nd_trace); skb->ingress_ifindex
@@ -6932,12 +6837,9 @@ __global__ __launch_bounds__(BLOCK) void k_run_write(uint32_t n, const uint32_t 
         __syncthreads();
     }
 }
-// rec: the packets' handle_policy records (the bucket's endpoint class), or null
-// (every bucket in class 0: the egress from-container pass).
 // single: single-packet buckets in packet-index order (the egress passes).
 // wide: the keys came from a frame front (gf_key_for(n, true)).
-static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullptr, bool single = false,
-                           bool wide = false) {
+static int schedule_groups(uint32_t n, hipStream_t s, bool single = false, bool wide = false) {
     Workspace &w = ws();
     const gf_key_cfg K = gf_key_for(n, wide);           // the width the keys were built with: the same rule, the same n
     auto grow = [](DevBuf &b, size_t want) -> int { return b.bytes >= want ? 0 : b.ensure(want); };
@@ -6948,7 +6850,6 @@ static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullpt
                     K.bits, s);
     const uint32_t nt = (n + GF_RUN_ITEMS - 1) / GF_RUN_ITEMS;
     if ((r = grow(w.tmp, sort_bytes + 256)) || (r = grow(w.tcnt, (size_t)nt * 4 + 16))) return r;
-    single = single && GF_SINGLE_ORDER && GF_NCLS == 1;
     if (single && ((r = grow(w.sb, (size_t)n * 4)) || (r = grow(w.st0, (size_t)nt * 4 + 16)) ||
                    (r = grow(w.st1, (size_t)nt * 4 + 16))))
         return r;
@@ -6979,12 +6880,11 @@ static int schedule_groups(uint32_t n, hipStream_t s, const gf_rec *rec = nullpt
         }();
         if (!lds_ok) return hip_ok(hipErrorInvalidValue, "k_bucket_sched LDS");
         uint32_t g = (n + GF_SCHED_ITEMS - 1) / GF_SCHED_ITEMS;
-        const gf_rec *lrec = GF_NCLS > 1 ? rec : nullptr;
         hipLaunchKernelGGL(k_bucket_hist, dim3(g), dim3(BLOCK), GF_SCHED_HBYTES, s, n, (const uint32_t *)w.off.p,
-                           (const uint32_t *)w.skeys.p, lrec, (const uint32_t *)w.perm.p, d_sched, K);
+                           (const uint32_t *)w.skeys.p, (const gf_rec *)nullptr, (const uint32_t *)w.perm.p, d_sched, K);
         hipLaunchKernelGGL(k_bucket_base, dim3(1), dim3(GF_LCAP), 0, s, d_sched);
         hipLaunchKernelGGL(k_bucket_order, dim3(g), dim3(BLOCK), GF_SCHED_HBYTES, s, n, (const uint32_t *)w.off.p,
-                           (const uint32_t *)w.skeys.p, lrec, (const uint32_t *)w.perm.p, d_sched, (uint2 *)w.order.p,
+                           (const uint32_t *)w.skeys.p, (const gf_rec *)nullptr, (const uint32_t *)w.perm.p, d_sched, (uint2 *)w.order.p,
                            single ? 1u : 0u, K);
         if (single) {                                   // (the words were cleared by k_run_count)
             hipLaunchKernelGGL(k_single_mark, dim3(std::min<uint32_t>((n + BLOCK - 1) / BLOCK, 8192u)), dim3(BLOCK), 0, s, n,
@@ -7595,7 +7495,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
     const bool pol_wave = egress;
     // a frame entry's records are written whole (no read-modify-write) unless its front left a flag
     // in them (keep_flags)
-    const bool pout_wo = GF_POUT_WO && P.pout && P.kind == PassKind::Frames && !P.keep_flags;
+    const bool pout_wo = P.pout && P.kind == PassKind::Frames && !P.keep_flags;
     const int noct = array_noct(a);                     // programs without conntrack: 0 none, 1 some, 2 all
     if (noct && egress) return -EOPNOTSUPP;             // (the egress entry point refuses such arrays)
     // trace notifications: the plain call decides and prepares here, the frame and egress
@@ -7657,7 +7557,7 @@ static int ingress_run(const std::shared_ptr<PolicyArray> &a, const gf_pkt_cols 
                            gf_key_for(n, wide), serial);
         if ((r = hip_ok(hipGetLastError(), "k_ing_serial_keys"))) return r;
     }
-    if (!prepared && noct != 2 && (r = schedule_groups(n, s, (const gf_rec *)w.rec.p, egress, wide))) return r;
+    if (!prepared && noct != 2 && (r = schedule_groups(n, s, egress, wide))) return r;
     host_mark("sched");
     // 4. handle_policy: one bucket per lane, buckets from the longest-first queue
     IngCtx X{};
@@ -7737,7 +7637,7 @@ static int ingress_prepare(const std::shared_ptr<PolicyArray> &a, const gf_pkt_c
     const int noct = array_noct(a);
     if (noct == 2) return 0;                            // no program with conntrack: no schedule
     if (noct == 1 && (r = noct_mark(a, n, s))) return r;
-    return schedule_groups(n, s, (const gf_rec *)ws().rec.p);
+    return schedule_groups(n, s);
 }
 
 // The stream that builds the next batch's schedule, and the events between the two.
@@ -8978,7 +8878,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     E.K = gf_key_for(n);
     E.ct4 = cfg_ct4; E.ct6 = cfg_ct6;
     if ((r = grow(ew.v6blk, (n + BLOCK - 1) / BLOCK))) return r;
-    E.v6blk = GF_EG_LEAN ? (uint8_t *)ew.v6blk.p : nullptr;
+    E.v6blk = (uint8_t *)ew.v6blk.p;
     E.s6out = (uint8_t *)ew.s6.p; E.d6out = (uint8_t *)ew.s6.p + 16;   // interleaved (IngCtx::a6_stride 32)
     memcpy(E.router6, node.router_ip6, 16); memcpy(E.host6, node.host_ip6, 16);
     if (lxc) {
@@ -9004,12 +8904,12 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     const bool conn = ct4m && !(strict & 1u) && !no_conn;
     uint32_t *d_rn = nullptr;                          // [0] related entries logged, [1] pair-group fallback
     if (conn) {
-        // the related entries' set (GF_EG_RSET): 4n slots keep it at most half full (<= 2n
+        // the related entries' set (RelSet): 4n slots keep it at most half full (<= 2n
         // writes, one per new connection in each pass); batches too large for 32-bit slot
         // numbers keep the write log
         uint64_t ns = 1024;
         while (ns < 4ull * n) ns *= 2;
-        const bool rset = GF_EG_RSET && ns <= (1ull << 31);
+        const bool rset = ns <= (1ull << 31);
         if ((r = grow(ew.keysP, (size_t)n * 4)) || (r = grow(ew.key2P, (size_t)n * 4)) || (r = grow(ew.rlog_n, 8)) ||
             (!rset && (r = grow(ew.rlog, (size_t)2 * n * GF_CTLOG_WORDS * 4))))
             return r;
@@ -9053,7 +8953,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
     {
         ProfScope ps("k_eg_front", s);
         // the IPv4 kernel's LDS rows: one per lane, the staged header bytes (<= GF_EG_STAGE)
-        const uint32_t eg_lds = GF_EG_DYN ? BLOCK * std::min<uint32_t>(S, GF_EG_STAGE) : BLOCK * GF_EG_STAGE;
+        const uint32_t eg_lds = BLOCK * std::min<uint32_t>(S, GF_EG_STAGE);
         hipLaunchKernelGGL(k_eg_front<4>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), eg_lds, s, fr, b->lxc_id, b->flow_hash,
                            E, (EgRec *)ew.erec.p, (uint32_t *)w.keys.p, out, fsink);
         hipLaunchKernelGGL(k_eg_front<6>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 16, s, fr, b->lxc_id, b->flow_hash,
@@ -9088,7 +8988,7 @@ static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch
             hip_ok(hipEventRecord(ew.ev_hz, s), "hz record"))
             return -EIO;
     }
-    if ((r = schedule_groups(n, s, nullptr, true))) return r;   // (reads only the front's keys: harmless on a flagged batch)
+    if ((r = schedule_groups(n, s, true))) return r;   // (reads only the front's keys: harmless on a flagged batch)
     host_mark("front+sched");
     // k_eg_groups is queued before the host looks at the ordering check: it reads the
     // check's flag itself and idles on a flagged batch (no map state changes then), so
