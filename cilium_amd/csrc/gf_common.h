@@ -1,5 +1,5 @@
 // gf_common.h — table layouts shared by the host shadow (gf_maps.cpp) and the
-// HIP kernels (gf_kernels.hip) of libgpuflow.
+// HIP kernels (gf_kernels.hip and the stage headers it includes) of libgpuflow.
 //
 // Exact-match hash maps (kernel BPF_MAP_TYPE_HASH / LRU_HASH semantics, see
 // DESIGN.md) use open addressing with linear probing over fixed-size slots:

@@ -21,7 +21,7 @@ namespace gf {
 //    config holds prog_lock() exclusively; classify calls hold it shared, so
 //    calls run concurrently with each other but never with a reconfiguration;
 //  * a classify call holds its stream's call context (the device workspaces
-//    of one call: CallCtx, gf_kernels.hip), the mutex of the cilium_policy array
+//    of one call: CallCtx, gf_host_ctx.h), the mutex of the cilium_policy array
 //    it runs and the mutex of every map it binds (MapLocks, address order, so two
 //    classify calls or a classify and a map operation never deadlock); on the
 //    device it is ordered after the last call that used any of those objects on
@@ -32,7 +32,7 @@ namespace gf {
 std::shared_mutex &prog_lock();
 
 // The device-side order of the calls that use one object (map, policy array):
-// the call context (one per stream, gf_kernels.hip) of the last such call.
+// the call context (one per stream, gf_host_ctx.h) of the last such call.
 struct CallCtx;
 struct OrderPt {
     CallCtx *last = nullptr;
@@ -348,7 +348,7 @@ uint64_t *stats_sink();
 void build_trie(const Map &m, std::vector<uint32_t> &root, std::vector<uint8_t> &nodes,
                 uint32_t &root_bits);
 
-// Chunked dump of a device-authoritative hash map (gf_kernels.hip): the FULL
+// Chunked dump of a device-authoritative hash map (gf_map_bulk.h): the FULL
 // slots of [start, start + range) in slot order, at most `max` of them, keys and
 // reference-layout values copied to the host arrays; *next = the slot after the
 // last one examined.

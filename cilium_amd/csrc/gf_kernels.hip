@@ -11,6 +11,15 @@
 //                (CT ordering rule)
 //   k_*_front    the frame entry points in front of it (pipeline, from-overlay, from-host)
 //   k_eg_*       bpf/bpf_lxc.c:427-738 from-container
+//
+// Host side, in include-only headers, each included exactly once below:
+//   gf_host_ctx.h       launch profiler, call contexts, check_cols, call order
+//   gf_host_programs.h  gf_parse_frames, the program loads, gf_xdp_classify, gf_lb_classify
+//   (between them and the next, in this file: PolicyPass, the flow-group schedule and k_run_*,
+//   the CT sweeps, ingress_run)
+//   gf_host_entry.h     the entry points over ingress_run, CT and proxy GC
+//   gf_map_bulk.h       k_bulk_*, k_dump_gather: gf_map_update_batch, gf_map_lookup_batch
+//   gf_host_egress.h    gf_lxc_egress_classify
 #include "gf_internal.h"
 #include "gf_device.h"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -6114,521 +6123,11 @@ __global__ __launch_bounds__(BLOCK) void k_rset_apply(RelSet R, const EgRec *ere
     if ((threadIdx.x & 63u) == 0u) atomicAdd(ct_count, tot);
 }
 
-// ================================================================ host: programs
-namespace {
+// ---- host: the launch profiler, call contexts (CallCtx), check_cols, the call order (CallOrder) ----
+#include "gf_host_ctx.h"
 
-// ---- launch profiler: HIP events on the launch stream around each kernel ----
-struct ProfEntry { std::string name; hipEvent_t a, b; };
-struct Prof {
-    bool on = false;
-    std::mutex mu;                     // concurrent classify calls record launches
-    std::vector<ProfEntry> pending;
-    std::map<std::string, std::pair<uint32_t, double>> acc;
-};
-Prof &prof() { static Prof p; return p; }
-struct ProfScope {
-    ProfEntry e{};
-    bool on;
-    hipStream_t s;
-    ProfScope(const char *n, hipStream_t s_) : on(prof().on), s(s_) {
-        if (!on) return;
-        e.name = n;
-        // timing only: no system-scope fence (an L2 writeback) at each launch boundary
-        (void)hipEventCreateWithFlags(&e.a, hipEventDisableSystemFence);
-        (void)hipEventCreateWithFlags(&e.b, hipEventDisableSystemFence);
-        (void)hipEventRecord(e.a, s);
-    }
-    ~ProfScope() {
-        if (!on) return;
-        (void)hipEventRecord(e.b, s);
-        std::lock_guard<std::mutex> g(prof().mu);
-        prof().pending.push_back(e);
-    }
-};
-void prof_drain() {
-    std::lock_guard<std::mutex> g(prof().mu);
-    for (auto &e : prof().pending) {
-        float ms = 0;
-        if (hipEventSynchronize(e.b) == hipSuccess && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
-            auto &a = prof().acc[e.name];
-            a.first++;
-            a.second += ms;
-        }
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    prof().pending.clear();
-}
-
-struct Workspace {
-    DevBuf rec, keys, skeys, perm, tcnt, off, tmp, sched, order;
-    DevBuf sb, st0, st1;               // single-packet buckets in index order (the egress passes)
-};
-// GF_HOST_PROF (diagnosis): the host time of a classify call's phases, one line
-// per call on stderr (where a call waits on the device, or spends its launches).
-struct HostMarks {
-    using clk = std::chrono::steady_clock;
-    bool on;
-    clk::time_point t0, last;
-    char buf[768];
-    int len = 0;
-    HostMarks *prev;
-    static HostMarks *&cur() { static thread_local HostMarks *c = nullptr; return c; }
-    HostMarks() : on(getenv("GF_HOST_PROF") != nullptr), prev(cur()) {
-        buf[0] = 0;
-        if (on) { t0 = last = clk::now(); cur() = this; }
-    }
-    static double us(clk::duration d) { return std::chrono::duration<double, std::micro>(d).count(); }
-    void mark(const char *what) {
-        if (!on) return;
-        const auto t = clk::now();
-        if (len < (int)sizeof buf - 40) len += snprintf(buf + len, sizeof buf - len, " %s %.0f", what, us(t - last));
-        last = t;
-    }
-    ~HostMarks() {
-        if (!on) return;
-        cur() = prev;
-        fprintf(stderr, "[gf] host us:%s | total %.0f\n", buf, us(clk::now() - t0));
-    }
-};
-void host_mark(const char *what) { if (HostMarks *m = HostMarks::cur()) m->mark(what); }
-// ---- call contexts: the device workspaces of one classify call.  Each HIP
-// stream has its own, so calls on different streams (over disjoint programs and
-// maps, see CallOrder) run concurrently, host and device; calls on one stream
-// take its context one at a time.  Workspace accessors keep one instance of
-// their type per context (CallCtx::get).
-}  // namespace
-namespace gf {
-struct CallCtx {
-    std::mutex mu;
-    hipEvent_t ev = nullptr;       // recorded at the end of every call in this context (made with the context)
-    std::atomic<bool> have{false}; // ev has been recorded once (read by other contexts' CallOrder)
-    int ws_slot = 0;      // gf_policy_ingress_classify_batches: schedule k+1 builds in one while k runs
-    std::map<const void *, std::shared_ptr<void>> bag;
-    template <class T> T &get(const void *tag) {
-        auto &p = bag[tag];
-        if (!p) p = std::make_shared<T>();
-        return *static_cast<T *>(p.get());
-    }
-};
-}  // namespace gf
-namespace {
-thread_local CallCtx *t_ctx = nullptr;
-CallCtx &ctx_for(hipStream_t s) {
-    static std::mutex mu;
-    static std::map<hipStream_t, std::unique_ptr<CallCtx>> all;
-    std::lock_guard<std::mutex> g(mu);
-    auto &c = all[s];
-    if (!c) {
-        c = std::make_unique<CallCtx>();
-        // the call-order event exists before any other thread can see the context
-        // (device-scope release: the event orders device work between streams)
-        if (hipEventCreateWithFlags(&c->ev, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) c->ev = nullptr;
-    }
-    return *c;
-}
-// The calling thread's context (map API paths outside a classify call: the
-// null stream's).
-CallCtx &cur_ctx() { return t_ctx ? *t_ctx : ctx_for(nullptr); }
-struct CtxScope {
-    CallCtx *prev, *c;
-    std::unique_lock<std::mutex> l;
-    explicit CtxScope(hipStream_t s) : prev(t_ctx), c(&ctx_for(s)), l(c->mu) { t_ctx = c; }
-    ~CtxScope() { t_ctx = prev; }
-};
-Workspace &ws() {
-    static const char tag = 0;
-    CallCtx &c = cur_ctx();
-    struct Two { Workspace w[2]; };
-    return c.get<Two>(&tag).w[c.ws_slot];
-}
-gf_event_ring &event_ring() { static gf_event_ring r{}; return r; }
-struct PipeWs {
-    DevBuf s6, d6;             // IPv6 addresses of the rewritten frames (read by handle_policy)
-};
-PipeWs &pipe_ws() { static const char tag = 0; return cur_ctx().get<PipeWs>(&tag); }
-
-int check_cols(const gf_pkt_cols *p) {
-    if (!p) return -EFAULT;
-    if (p->n == 0) return 0;
-    if (!p->len || !p->ethertype || !p->saddr4 || !p->daddr4 || !p->proto || !p->l4_off || !p->l4w0 || !p->l4w3)
-        return -EFAULT;
-    return 1;
-}
-
-uint32_t grid_for(uint32_t n) {
-    uint32_t g = (n + BLOCK - 1) / BLOCK;
-    return g < 1 ? 1 : (g > 65535u * 8 ? 65535u * 8 : g);
-}
-// Grid of the one-packet-per-lane stream kernels (k_xdp, k_lb): capped at
-// GF_STREAM_GRID blocks (grid-stride beyond) so the per-block counter flush
-// stays a few thousand atomics per bin; 0 = one lane per packet.  Measured
-// (config 3, k_lb, 16M packets): uncapped 0.86 ms, 2k 0.85, 4k 0.72, 16k 0.68.
-#ifndef GF_STREAM_GRID
-#define GF_STREAM_GRID 16384
-#endif
-// GPUFLOW_STREAM_GRID overrides the cap (the GPU tests force a few blocks so
-// every block runs several tiles of the grid-stride loop).
-uint32_t stream_grid_cap() {
-    const char *e = getenv("GPUFLOW_STREAM_GRID");
-    return e ? (uint32_t)strtoul(e, nullptr, 10) : (uint32_t)GF_STREAM_GRID;
-}
-uint32_t stream_grid(uint32_t n, uint32_t per_block = BLOCK) {
-    const uint32_t g = n == 0 ? 1u : (n + per_block - 1) / per_block, cap = stream_grid_cap();
-    const uint32_t lim = cap ? cap : 65535u * 8;      // grid-stride covers the rest
-    return g > lim ? lim : g;
-}
-
-int push_map(const std::shared_ptr<Map> &m, hipStream_t s) { return m ? m->push(s) : 0; }
-// bpf_lb's launch descriptor: the service maps (pushed by the caller) and the program's flags
-LbDev lb_dev(const ProgLb &p) {
-    LbDev L{};
-    if (p.lb4) L.s4 = p.lb4->hdesc();
-    if (p.lb6) L.s6 = p.lb6->hdesc();
-    L.flags = p.cfg.flags;
-    return L;
-}
-// The v4 prefixes as DIR-24-8 tables for XdpDev (GF_XDP_DIR24=1: the A/B against
-// the trie walk), when they build.
-void xdp_dir(const std::shared_ptr<Map> &l4, XdpDev &x, hipStream_t s) {
-    const char *e = getenv("GF_XDP_DIR24");       // read per call: a test flips it in-process
-    const bool on = e && atoi(e) != 0;
-    x.d24 = nullptr; x.d8 = nullptr;
-    if (on && l4 && l4->dir24(s, &x.d24, &x.d8)) { x.d24 = nullptr; x.d8 = nullptr; }
-}
-// The prefilter's compact address sets (Map::addr_set) for XdpDev, when they build.
-void xdp_sets(const std::shared_ptr<Map> &h4, const std::shared_ptr<Map> &lxc, XdpDev &x, hipStream_t s) {
-    static const bool no_sets = getenv("GF_XDP_NOSETS") != nullptr;     // diagnosis: the hash tables
-    if (no_sets) return;
-    if (h4 && h4->addr_set(8, 8192, s, &x.h4set, &x.h4bits, &x.h4zero)) x.h4set = nullptr;
-    if (lxc && lxc->addr_set(20, 8192, s, &x.lxset, &x.lxbits, &x.lxzero)) x.lxset = nullptr;
-}
-
-// ---- device-side order of the calls that share an object.  Every map a call
-// binds and the cilium_policy array it runs remember the call context (stream)
-// of the last call that used them (OrderPt): a call first waits on the end event
-// of each other context found there (one wait per context, on its latest call —
-// a conservative bound), so a kernel still reading or writing a map replica (or a
-// program table) finishes before this call pushes into it or runs over it; at its
-// end the call records its context's event once and marks every object with its
-// context (under the objects' locks).  The workspaces are per stream (CallCtx), so
-// calls over disjoint objects on different streams do not wait on each other.
-// With an event ring set, calls append to it in turn.
-std::mutex &ring_mu() { static std::mutex m; return m; }
-OrderPt &ring_ord() { static OrderPt o; return o; }
-struct CallOrder {
-    hipStream_t s;
-    CallCtx *me;
-    std::vector<OrderPt *> pts;
-    std::unique_lock<std::mutex> ring;
-    CallOrder(hipStream_t s_, std::vector<OrderPt *> p) : s(s_), me(&cur_ctx()), pts(std::move(p)) {
-        if (event_ring().records) {
-            ring = std::unique_lock<std::mutex>(ring_mu());
-            pts.push_back(&ring_ord());
-        }
-        CallCtx *waited[8];
-        int nw = 0;
-        for (OrderPt *o : pts) {
-            CallCtx *c = o->last;
-            if (!c || c == me || !c->have.load(std::memory_order_acquire)) continue;
-            bool seen = false;
-            for (int k = 0; k < nw; k++) seen |= waited[k] == c;
-            if (seen) continue;
-            (void)hipStreamWaitEvent(s, c->ev, 0);
-            if (nw < 8) waited[nw++] = c;
-        }
-    }
-    CallOrder(hipStream_t s_, const MapLocks &L, PolicyArray *a = nullptr) : CallOrder(s_, order_pts(L, a)) {}
-    static std::vector<OrderPt *> order_pts(const MapLocks &L, PolicyArray *a) {
-        std::vector<OrderPt *> v;
-        for (Map *m : L.held) v.push_back(&m->ord);
-        if (a) v.push_back(&a->ord);
-        return v;
-    }
-    ~CallOrder() {
-        if (!me->ev || hipEventRecord(me->ev, s) != hipSuccess) return;
-        me->have.store(true, std::memory_order_release);
-        for (OrderPt *o : pts) o->last = me;
-    }
-};
-void lock_lxc_maps(MapLocks &L, const std::shared_ptr<ProgLxc> &p) {
-    for (auto m : {p->policy, p->ct4, p->ct6, p->cidr4, p->cidr6, p->revnat4, p->revnat6, p->lb4, p->ipcache,
-                   p->cidr4e, p->lb6, p->cidr6e})
-        L.add(m);
-}
-void lock_array_maps(MapLocks &L, const std::shared_ptr<PolicyArray> &a) {
-    for (auto &kv : a->slots) lock_lxc_maps(L, kv.second);
-    L.add(proxy_map(4)); L.add(proxy_map(6)); L.add(node_map(1)); L.add(node_map(2));
-}
-void lock_xdp_maps(MapLocks &L, const ProgXdp &x) { L.add(x.m4h); L.add(x.m4l); L.add(x.m6h); L.add(x.m6l); L.add(x.lxc); }
-
-
-// blocks of BLOCK threads that fill the device at `per_cu` blocks per CU
-uint32_t resident_blocks(uint32_t per_cu) {
-    static const int cus = [] {                   // thread-safe one-time init (concurrent calls)
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
-            c = 256;
-        return c;
-    }();
-    return (uint32_t)cus * per_cu;
-}
-
-}  // namespace
-
-extern "C" {
-
-int gf_parse_frames(const gf_frames *fr, gf_pkt_cols_out *o, void *stream) {
-    if (!fr || !o) return -EFAULT;
-    if (fr->n == 0) return 0;
-    if (!fr->snap || !fr->len || !o->ethertype || !o->saddr4 || !o->daddr4 || !o->proto || !o->l4_off ||
-        !o->l4w0 || !o->l4w3)
-        return -EFAULT;
-    if (fr->snap_stride < 14) return -EINVAL;
-    ProfScope ps("k_parse", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_parse, dim3(grid_for(fr->n)), dim3(BLOCK), 0, (hipStream_t)stream, *fr, *o);
-    return hip_ok(hipGetLastError(), "k_parse");
-}
-
-int gf_xdp_prog_load(const gf_xdp_cfg *cfg) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!cfg) return -EFAULT;
-    auto p = std::make_shared<ProgXdp>();
-    p->cfg = *cfg;
-    auto bind = [](int h, uint32_t ksz, bool lpm, std::shared_ptr<Map> &out) -> int {
-        if (!h) return 0;
-        auto m = get_map(h);
-        if (!m) return -EBADF;
-        if (m->ksz != ksz || m->is_lpm() != lpm) return -EINVAL;
-        out = m;
-        return 0;
-    };
-    int r;
-    if ((r = bind(cfg->cidr4_hmap, 8, false, p->m4h))) return r;
-    if ((r = bind(cfg->cidr4_lmap, 8, true, p->m4l))) return r;
-    if ((r = bind(cfg->cidr6_hmap, 20, false, p->m6h))) return r;
-    if ((r = bind(cfg->cidr6_lmap, 20, true, p->m6l))) return r;
-    if ((r = bind(cfg->lxc_map, 20, false, p->lxc))) return r;
-    if (!p->lxc) return -EINVAL;
-    return new_handle(p);
-}
-
-int gf_xdp_classify(int prog, const gf_pkt_cols *pkts, uint8_t *verdict, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgXdp>(prog);
-    if (!p) return -EBADF;
-    int c = check_cols(pkts);
-    if (c <= 0) return c;
-    if (!verdict) return -EFAULT;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    MapLocks L;
-    lock_xdp_maps(L, *p);
-    L.lock();
-    CallOrder co(s, L);
-    int r;
-    if ((r = push_map(p->m4h, s)) || (r = push_map(p->m4l, s)) || (r = push_map(p->m6h, s)) ||
-        (r = push_map(p->m6l, s)) || (r = push_map(p->lxc, s)))
-        return r;
-    XdpDev x{};
-    xdp_sets(p->m4h, p->lxc, x, s);
-    if (p->m4h) { x.h4 = p->m4h->hdesc(); x.has_h4 = 1; }
-    if (p->m6h) { x.h6 = p->m6h->hdesc(); x.has_h6 = 1; }
-    if (p->m4l) x.l4 = p->m4l->tdesc();
-    if (p->m6l) x.l6 = p->m6l->tdesc();
-    xdp_dir(p->m4l, x, s);
-    x.lxc = p->lxc->hdesc();
-    ProfScope ps("k_xdp", s);
-    // The LDS variant when the LPM map has a 16-bit root (its summary is 16 KB);
-    // the /32 hash and the endpoint keys join it while they fit.
-    static const bool no_lds = getenv("GF_XDP_NOLDS") != nullptr;     // diagnosis: the HBM-only kernel
-    if (!no_lds && x.l4.rsum && x.has_h4 && x.l4.addr_bytes == 4) {
-        static const uint32_t cap = getenv("GF_XDP_LDS_KB") ? 1024u * (uint32_t)atoi(getenv("GF_XDP_LDS_KB")) : 48u * 1024u;
-        XdpLds L{};
-        // the /32 hash and the endpoint keys as compact address sets (4 B a slot), else
-        // their slot arrays when those fit the budget
-        L.h4set = x.h4set; L.h4bits = x.h4bits; L.h4zero = x.h4zero;
-        L.lxset = x.lxset; L.lxbits = x.lxbits; L.lxzero = x.lxzero;
-        const uint64_t hb = (uint64_t)(x.h4.mask + 1) * x.h4.slot_size, lb = (uint64_t)(x.lxc.mask + 1) * x.lxc.slot_size;
-        if (!L.h4set && x.h4.slots && x.h4.ksz == 8 && hb % 16 == 0 && GF_TRIE_RSUM_BYTES + hb <= std::min(cap, 96u * 1024u))
-            L.h4_bytes = (uint32_t)hb;
-        const uint32_t h4b = L.h4set ? 4u << L.h4bits : L.h4_bytes;
-        if (!L.lxset && x.lxc.slots && x.lxc.ksz == 20 && lb % 16 == 0 && GF_TRIE_RSUM_BYTES + h4b + lb <= cap)
-            L.lxc_bytes = (uint32_t)lb;
-        const uint32_t lds = GF_TRIE_RSUM_BYTES + h4b + (L.lxset ? 4u << L.lxbits : L.lxc_bytes);
-        // the address sets count against the budget too: larger maps take k_xdp,
-        // which reads the same sets and the root summary through L2
-        static std::atomic<uint32_t> lds_set{0};
-        bool fits = lds <= std::max(cap, GF_TRIE_RSUM_BYTES);
-        if (fits && lds > lds_set.load()) {
-            fits = hipFuncSetAttribute((const void *)k_xdp_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) ==
-                   hipSuccess;
-            if (fits) {
-                uint32_t cur = lds_set.load();
-                while (lds > cur && !lds_set.compare_exchange_weak(cur, lds)) {}
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        if (fits) {
-        const uint32_t per_cu = lds <= 78u * 1024u ? 2u : 1u;
-        static const uint32_t grid_env = getenv("GF_XDP_GRID") ? (uint32_t)atoi(getenv("GF_XDP_GRID")) : 0u;   // diagnosis
-        const uint32_t grid = grid_env ? grid_env
-                                       : std::max<uint32_t>(1u, std::min<uint32_t>(resident_blocks(per_cu), (pkts->n + 1023) / 1024));
-        hipLaunchKernelGGL(k_xdp_lds, dim3(grid), dim3(1024), lds, s, *pkts, x, L, verdict,
-                           (unsigned long long *)stats_sink());
-        return hip_ok(hipGetLastError(), "k_xdp_lds");
-        }
-    }
-    hipLaunchKernelGGL(k_xdp, dim3(stream_grid(pkts->n)), dim3(BLOCK), 0, s, *pkts, x, verdict,
-                       (unsigned long long *)stats_sink());
-    return hip_ok(hipGetLastError(), "k_xdp");
-}
-
-int gf_lb_prog_load(const gf_lb_cfg *cfg) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!cfg) return -EFAULT;
-    auto p = std::make_shared<ProgLb>();
-    p->cfg = *cfg;
-    if (cfg->lb4_services) {
-        p->lb4 = get_map(cfg->lb4_services);
-        if (!p->lb4) return -EBADF;
-        if (p->lb4->ksz != 8 || p->lb4->vsz != 12 || p->lb4->is_lpm()) return -EINVAL;
-    }
-    if (cfg->lb6_services) {
-        p->lb6 = get_map(cfg->lb6_services);
-        if (!p->lb6) return -EBADF;
-        if (p->lb6->ksz != 20 || p->lb6->vsz != 24 || p->lb6->is_lpm()) return -EINVAL;
-    }
-    return new_handle(p);
-}
-
-int gf_lb_classify(int prog, const gf_pkt_cols *pkts, gf_lb_out *out, uint8_t *nd6, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgLb>(prog);
-    if (!p) return -EBADF;
-    int c = check_cols(pkts);
-    if (c <= 0) return c;
-    if (!out) return -EFAULT;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    MapLocks ML;
-    ML.add(p->lb4); ML.add(p->lb6);
-    ML.lock();
-    CallOrder co(s, ML);
-    int r;
-    if ((r = push_map(p->lb4, s)) || (r = push_map(p->lb6, s))) return r;
-    const LbDev L = lb_dev(*p);
-    ProfScope ps("k_lb", s);
-    hipLaunchKernelGGL(k_lb, dim3(stream_grid(pkts->n)), dim3(BLOCK), 0, s, *pkts, L, out, nd6,
-                       (unsigned long long *)stats_sink());
-    return hip_ok(hipGetLastError(), "k_lb");
-}
-
-int gf_lxc_prog_load(const gf_lxc_cfg *cfg) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!cfg) return -EFAULT;
-    if (cfg->n_l4_ingress > GF_MAX_L4_INGRESS || cfg->n_l4_egress > GF_MAX_L4_INGRESS ||
-        cfg->n_portmap > GF_MAX_PORTMAP)
-        return -E2BIG;
-    // CONNTRACK undefined: CFG_L3L4_* is refused (bpf/lib/l4.h:138-139); the CT maps and
-    // CONNTRACK_ACCOUNTING mean nothing to the stub ct_* (conntrack.h:582-617)
-    const bool noct = (cfg->flags & GF_LXC_F_NO_CONNTRACK) != 0;
-    if (noct && (cfg->n_l4_ingress || cfg->n_l4_egress)) return -EINVAL;
-    if (noct && (cfg->flags & GF_LXC_F_DEBUG)) return -EOPNOTSUPP;   // (the CT-off kernel sends no debug messages)
-    // GF_LXC_F_LB_DEBUG needs no rule: without DEBUG cilium_dbg_lb is the empty cilium_dbg (dbg.h:134-233)
-    auto p = std::make_shared<ProgLxc>();
-    p->cfg = *cfg;
-    if (noct) { p->cfg.ct_map4 = p->cfg.ct_map6 = 0; p->cfg.flags &= ~GF_LXC_F_CT_ACCOUNTING; }
-    struct B { int h; uint32_t k, v; bool lpm; std::shared_ptr<Map> *out; };
-    B binds[] = {
-        {cfg->policy_map, 8, 24, false, &p->policy}, {p->cfg.ct_map4, 14, 48, false, &p->ct4},
-        {p->cfg.ct_map6, 40, 48, false, &p->ct6},      {cfg->cidr4_ingress_map, 8, 0, true, &p->cidr4},
-        {cfg->cidr6_ingress_map, 20, 0, true, &p->cidr6}, {cfg->revnat4_map, 2, 6, false, &p->revnat4},
-        {cfg->revnat6_map, 2, 18, false, &p->revnat6},
-        {cfg->lb4_services, 8, 12, false, &p->lb4},      {cfg->ipcache_map, 20, 8, false, &p->ipcache},
-        {cfg->cidr4_egress_map, 8, 0, true, &p->cidr4e}, {cfg->lb6_services, 20, 24, false, &p->lb6},
-        {cfg->cidr6_egress_map, 20, 0, true, &p->cidr6e},
-    };
-    for (auto &b : binds) {
-        if (!b.h) continue;
-        auto m = get_map(b.h);
-        if (!m) return -EBADF;
-        if (m->ksz != b.k || m->is_lpm() != b.lpm || (!b.lpm && m->vsz != b.v)) return -EINVAL;
-        *b.out = m;
-    }
-    MapLocks L;
-    lock_lxc_maps(L, p);
-    L.lock();
-    if (p->ct4) { p->ct4->set_hash_mode(GF_HASH_CT); p->ct4->set_value_codec(GF_VCODEC_CT); p->ct4->make_fixed_capacity(gf_ct_slot_factor(p->ct4->ksz)); }
-    if (p->ct6) { p->ct6->set_hash_mode(GF_HASH_CT); p->ct6->set_value_codec(GF_VCODEC_CT); p->ct6->make_fixed_capacity(gf_ct_slot_factor(p->ct6->ksz)); }
-    if (p->policy) { p->policy->set_hash_mode(GF_HASH_POLICY); p->policy->set_value_codec(GF_VCODEC_POL); }
-    return new_handle(p);
-}
-
-int gf_set_event_ring(const gf_event_ring *ring) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!ring) { event_ring() = gf_event_ring{}; return 0; }
-    if (!ring->records || !ring->count) return -EFAULT;
-    event_ring() = *ring;
-    return 0;
-}
-
-int gf_prof_enable(int on) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    prof_drain();
-    prof().acc.clear();
-    prof().on = on != 0;
-    return 0;
-}
-
-int gf_prof_read(gf_prof_rec *out, int max) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (max < 0 || (max > 0 && !out)) return -EFAULT;
-    prof_drain();
-    int k = 0;
-    for (auto &kv : prof().acc) {
-        if (k >= max) break;
-        memset(&out[k], 0, sizeof out[k]);
-        strncpy(out[k].name, kv.first.c_str(), sizeof(out[k].name) - 1);
-        out[k].count = kv.second.first;
-        out[k].total_ms = kv.second.second;
-        k++;
-    }
-    return k;
-}
-
-int gf_policy_array_create(void) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    return new_handle(std::make_shared<PolicyArray>());
-}
-
-int gf_policy_array_update(int array, uint32_t lxc_id, int prog) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    auto a = get_as<PolicyArray>(array);
-    if (!a) return -EBADF;
-    if (lxc_id > 0xffff) return -E2BIG;
-    if (prog) {
-        auto po = get_as<ProgLxc>(prog);
-        if (!po) return -EINVAL;
-        a->slots[lxc_id] = po;
-    } else {
-        a->slots.erase(lxc_id);
-    }
-    a->dirty = true;
-    a->gen++;
-    size_t off = 0;                                     // programs without conntrack: none, some, every one
-    for (auto &kv : a->slots)
-        if (kv.second->cfg.flags & GF_LXC_F_NO_CONNTRACK) off++;
-    a->noct = !off ? 0 : off == a->slots.size() ? 2 : 1;
-    a->dbg = false;                                     // any program with DEBUG
-    for (auto &kv : a->slots)
-        if (kv.second->cfg.flags & GF_LXC_F_DEBUG) a->dbg = true;
-    return 0;
-}
-
-}  // extern "C"
+// ---- host: program loads and the column calls: gf_parse_frames, gf_xdp_*, gf_lb_*, gf_lxc_prog_load ----
+#include "gf_host_programs.h"
 
 // handle_policy over a batch (caller holds prog_lock and the maps' locks, and checked the columns).
 // skip (DEVICE, may be null): packets a pipeline ended before the tail call.
@@ -7757,1470 +7256,15 @@ static int front_call(const std::shared_ptr<PolicyArray> &policy, const gf_frame
     return ingress_run(policy, &c2, now_sec, s, pass);
 }
 
-extern "C" {
-
-int gf_policy_ingress_classify_batches(int array, uint32_t nb, const gf_pkt_cols *const *batches,
-                                       const uint32_t *now_sec, gf_ingress_out *const *outs, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto a = get_as<PolicyArray>(array);
-    if (!a) return -EBADF;
-    if (nb && (!batches || !now_sec || !outs)) return -EFAULT;
-    for (uint32_t k = 0; k < nb; k++) {
-        const int c = check_cols(batches[k]);
-        if (c < 0) return c;
-        if (c && !outs[k]) return -EFAULT;
-        if (batches[k]->n > (1u << 30)) return -E2BIG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    std::lock_guard<std::mutex> ag(a->mu);
-    MapLocks L;
-    lock_array_maps(L, a);
-    L.lock();
-    CallOrder co(s, L, a.get());
-    PipeSync &P = pipe_sync();
-    int r;
-    if ((r = P.init())) return r;
-    std::vector<std::shared_ptr<ProgLxc>> progs;
-    if ((r = prog_table(a, s, progs))) return r;          // the program table k_ing_pack reads, on s
-    if (hip_ok(hipEventRecord(P.ready, s), "ready") || hip_ok(hipStreamWaitEvent(P.aux, P.ready, 0), "aux wait"))
-        return -EIO;
-    auto prep = [&](uint32_t k) -> int {                  // batch k's schedule on the aux stream, workspace k & 1
-        const int slot = (int)(k & 1u);
-        if (k >= 2 && hip_ok(hipStreamWaitEvent(P.aux, P.done[slot], 0), "aux wait done")) return -EIO;
-        cur_ctx().ws_slot = slot;
-        int rr = batches[k]->n ? ingress_prepare(a, batches[k], P.aux) : 0;
-        cur_ctx().ws_slot = 0;
-        if (rr) return rr;
-        return hip_ok(hipEventRecord(P.built[slot], P.aux), "built") ? -EIO : 0;
-    };
-    if (nb && (r = prep(0))) return r;
-    for (uint32_t k = 0; k < nb; k++) {
-        if (k + 1 < nb && (r = prep(k + 1))) return r;    // overlaps handle_policy of batch k
-        const int slot = (int)(k & 1u);
-        if (hip_ok(hipStreamWaitEvent(s, P.built[slot], 0), "wait built")) return -EIO;
-        if (batches[k]->n) {
-            cur_ctx().ws_slot = slot;
-            PolicyPass pass;
-            pass.out = outs[k];
-            pass.prepared = true;                         // (prep(k) built the schedule)
-            r = ingress_run(a, batches[k], now_sec[k], s, pass);
-            cur_ctx().ws_slot = 0;
-            if (r) return r;
-        }
-        if (hip_ok(hipEventRecord(P.done[slot], s), "done")) return -EIO;
-    }
-    return 0;
-}
-
-int gf_policy_ingress_classify(int array, const gf_pkt_cols *pkts, uint32_t now_sec, gf_ingress_out *out,
-                               void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto a = get_as<PolicyArray>(array);
-    if (!a) return -EBADF;
-    int c = check_cols(pkts);
-    if (c <= 0) return c;
-    if (!out) return -EFAULT;
-    if (pkts->n > (1u << 30)) return -E2BIG;
-    CtxScope cx((hipStream_t)stream);
-    std::lock_guard<std::mutex> ag(a->mu);
-    MapLocks L;
-    lock_array_maps(L, a);
-    L.lock();
-    CallOrder co((hipStream_t)stream, L, a.get());
-    PolicyPass pass;
-    pass.out = out;
-    return ingress_run(a, pkts, now_sec, (hipStream_t)stream, pass);
-}
-
-// ---- full pipeline ----
-int gf_pipeline_load(const gf_pipeline_cfg *cfg) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!cfg) return -EFAULT;
-    auto p = std::make_shared<ProgPipe>();
-    p->cfg = *cfg;
-    if (cfg->xdp_prog) {
-        p->xdp = get_as<ProgXdp>(cfg->xdp_prog);
-        if (!p->xdp) return -EBADF;
-    }
-    if (cfg->lb_prog) {
-        p->lb = get_as<ProgLb>(cfg->lb_prog);
-        if (!p->lb) return -EBADF;
-    }
-    auto m = get_map(cfg->netdev.lxc_map);
-    if (!m) return -EBADF;
-    if (!lxc_map_ok(*m)) return -EINVAL;
-    p->lxc = m;
-    // ENCAP_IFINDEX for the netdev stage is the node's: it must be defined, with a tunnel map to look up
-    if ((cfg->netdev.flags & GF_NETDEV_F_ENCAP) && (!node_cfg().encap_ifindex || !node_map(2))) return -EINVAL;
-    p->policy = get_as<PolicyArray>(cfg->policy_array);
-    if (!p->policy) return -EBADF;
-    return new_handle(p);
-}
-
-int gf_pipeline_classify(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_pipeline_out *out,
-                         uint8_t *nd6, uint8_t *snap_out, void *stream) {
-    return gf_pipeline_classify_tunnel(pipe, b, now_sec, out, nd6, snap_out, nullptr, stream);
-}
-
-int gf_pipeline_classify_tunnel(int pipe, const gf_pipe_batch *b, uint32_t now_sec, gf_pipeline_out *out,
-                                uint8_t *nd6, uint8_t *snap_out, uint32_t *tunnel_ip, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgPipe>(pipe);
-    if (!p) return -EBADF;
-    if (!b) return -EFAULT;
-    const gf_frames &fr = b->frames;
-    int r = frames_check(fr, out != nullptr);
-    if (r <= 0) return r;
-    hipStream_t s = (hipStream_t)stream;
-    HostMarks hm;
-    CtxScope cx(s);
-    std::lock_guard<std::mutex> ag(p->policy->mu);
-    MapLocks L;
-    if (p->xdp) lock_xdp_maps(L, *p->xdp);
-    if (p->lb) { L.add(p->lb->lb4); L.add(p->lb->lb6); }
-    L.add(p->lxc);
-    lock_array_maps(L, p->policy);
-    L.lock();
-    CallOrder co(s, L, p->policy.get());
-    PipeDev P{};
-    if (p->xdp) {
-        auto &x = *p->xdp;
-        if ((r = push_map(x.m4h, s)) || (r = push_map(x.m4l, s)) || (r = push_map(x.m6h, s)) ||
-            (r = push_map(x.m6l, s)) || (r = push_map(x.lxc, s)))
-            return r;
-        if (x.m4h) { P.x.h4 = x.m4h->hdesc(); P.x.has_h4 = 1; }
-        if (x.m6h) { P.x.h6 = x.m6h->hdesc(); P.x.has_h6 = 1; }
-        if (x.m4l) P.x.l4 = x.m4l->tdesc();
-        if (x.m6l) P.x.l6 = x.m6l->tdesc();
-        P.x.lxc = x.lxc->hdesc();
-        xdp_sets(x.m4h, x.lxc, P.x, s);
-        xdp_dir(x.m4l, P.x, s);
-        P.has_xdp = 1;
-    }
-    if (p->lb) {
-        if ((r = push_map(p->lb->lb4, s)) || (r = push_map(p->lb->lb6, s))) return r;
-        P.L = lb_dev(*p->lb);
-        P.lb_redirect_ifindex = p->lb->cfg.redirect_ifindex;
-        P.has_lb = 1;
-    }
-    if ((r = push_map(p->lxc, s))) return r;
-    const gf_netdev_cfg &nd = p->cfg.netdev;
-    P.nd.lx = lxc_dev(p->lxc, s);
-    P.nd.flags = nd.flags;
-    P.nd.fixed_secctx = nd.fixed_secctx;
-    memcpy(P.nd.router6, nd.router_ip6, 8);
-    // GF_NETDEV_F_HANDLE_NS / _ENCAP: k_nd_front; neither set: k_pipe_front
-    const bool ndx = nd.flags & (GF_NETDEV_F_HANDLE_NS | GF_NETDEV_F_ENCAP);
-    NdxDev X{};
-    if (ndx) {
-        memcpy(X.router6, nd.router_ip6, 16);
-        X.tunnel_ip = tunnel_ip;
-        if (nd.flags & GF_NETDEV_F_ENCAP) {
-            const gf_node_cfg &node = node_cfg();
-            auto tun = node_map(2);
-            if (!tun || !node.encap_ifindex) return -EINVAL;   // the node was reconfigured since gf_pipeline_load
-            if ((r = push_map(tun, s))) return r;
-            X.enc = encap_dev(node, tun, s);
-        }
-    } else if (tunnel_ip) {
-        if (hip_ok(hipMemsetAsync(tunnel_ip, 0, (size_t)fr.n * 4, s), "tunnel_ip")) return -EIO;
-    }
-    PolicyPass pass;
-    const uint32_t trace = (nd.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_STACK | (GF_STAGE_NETDEV << 8)) : 0u;
-    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, pass, trace, nd.ingress_ifindex, P.vec_copy,
-                      P.tcap_in, ndx ? "k_nd_front" : "k_pipe_front",
-                      [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
-        if (ndx)
-            launch_nt(k_nd_front<256>, k_nd_front<128>, f, fr, b->tc_index, b->flow_hash, P, X, slot_of, rec, keys, f.s6,
-                      f.d6, out, nd6, snap_out, f.sink, f.K);
-        else
-            launch_nt(k_pipe_front<256>, k_pipe_front<128>, f, fr, b->tc_index, b->flow_hash, P, slot_of, rec, keys, f.s6,
-                      f.d6, out, nd6, snap_out, f.sink, f.K);
-    });
-}
-
-// ---- bpf_lb over frames ----
-int gf_lb_prog_set_dstmac(int prog, const uint8_t mac[6]) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgLb>(prog);
-    if (!p) return -EBADF;
-    if (!(p->cfg.flags & GF_LB_F_REDIRECT)) return -EINVAL;   // LB_DSTMAC sits inside #ifdef LB_REDIRECT
-    p->has_dstmac = mac != nullptr;
-    if (mac) memcpy(p->dstmac, mac, 6); else memset(p->dstmac, 0, 6);
-    return 0;
-}
-
-int gf_lb_classify_frames(int prog, const gf_frames *frames, const uint32_t *flow_hash, gf_lb_out *out,
-                          uint8_t *nd6, uint8_t *snap_out, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgLb>(prog);
-    if (!p) return -EBADF;
-    if (!frames) return -EFAULT;
-    const gf_frames &fr = *frames;
-    int r = frames_check(fr, out != nullptr);
-    if (r <= 0) return r;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    MapLocks ML;
-    ML.add(p->lb4); ML.add(p->lb6);
-    ML.lock();
-    CallOrder co(s, ML);
-    if ((r = push_map(p->lb4, s)) || (r = push_map(p->lb6, s))) return r;
-    const LbDev L = lb_dev(*p);
-    LbFrDev F{};
-    if (p->has_dstmac) {
-        F.has_mac = 1;
-        memcpy(&F.mac_lo, p->dstmac, 4);
-        F.mac_hi = (uint32_t)p->dstmac[4] | ((uint32_t)p->dstmac[5] << 8);
-    }
-    const FrontLaunch f = front_geometry(fr, snap_out, s, F.vec_copy);   // the fronts' tiles
-    {
-        ProfScope ps("k_lb_frames", s);
-        launch_nt(k_lb_frames<256>, k_lb_frames<128>, f, fr, flow_hash, L, F, out, nd6, snap_out, f.sink);
-        if ((r = hip_ok(hipGetLastError(), "k_lb_frames"))) return r;
-    }
-    // send_drop_notify_error's records (bpf_lb.c:194-195): the drop list of ev_list without a trace.
-    // gf_lb_out has no stage byte; a SHOT record is zero past its reason, so byte 2 reads as
-    // GF_STAGE_NONE, which ev_list gives the caller's record: zeros for source, labels and ifindex,
-    // as for GF_STAGE_LB.
-    EvSrc E{};
-    E.recs = (const uint8_t *)out;
-    E.stride = sizeof(gf_lb_out); E.act_off = 0; E.stage_off = 2;
-    E.len = fr.len; E.flow_hash = flow_hash; E.n = fr.n;
-    E.snap = snap_out ? snap_out : fr.snap; E.snap_stride = fr.snap_stride;
-    return emit_drop_events(E, s);
-}
-
-// ---- from-overlay ----
-int gf_overlay_load(const gf_overlay_cfg *cfg) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!cfg) return -EFAULT;
-    auto p = std::make_shared<ProgOverlay>();
-    p->cfg = *cfg;
-    auto m = get_map(cfg->lxc_map);
-    if (!m) return -EBADF;
-    if (!lxc_map_ok(*m)) return -EINVAL;
-    p->lxc = m;
-    p->policy = get_as<PolicyArray>(cfg->policy_array);
-    if (!p->policy) return -EBADF;
-    return new_handle(p);
-}
-
-// gf_overlay_classify (with_opts false: a Geneve program is refused) and gf_overlay_classify_opts.
-static int overlay_call(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts *opts, bool with_opts,
-                        uint32_t now_sec, gf_pipeline_out *out, uint8_t *snap_out, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgOverlay>(ovl);
-    if (!p) return -EBADF;
-    if (!b) return -EFAULT;
-    const bool geneve = p->cfg.flags & GF_OVERLAY_F_GENEVE;
-    if (geneve && !with_opts) return -EINVAL;          // ENCAP_GENEVE reads options: gf_overlay_classify_opts
-    const gf_frames &fr = b->frames;
-    int r = frames_check(fr, out && b->tunnel_id);
-    if (r <= 0) return r;
-    OvlOpt<true> G{};
-    if (geneve) {                                      // a VXLAN program ignores opts
-        if (!opts || !opts->opt || !opts->opt_len) return -EFAULT;
-        if (opts->opt_stride < 4 || opts->opt_stride > 64 || (opts->opt_stride & 3u) || ((uintptr_t)opts->opt & 3u))
-            return -EINVAL;
-        G.opt = opts->opt; G.len = opts->opt_len; G.stride = opts->opt_stride;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    HostMarks hm;
-    CtxScope cx(s);
-    std::lock_guard<std::mutex> ag(p->policy->mu);
-    MapLocks L;
-    L.add(p->lxc);
-    lock_array_maps(L, p->policy);
-    L.lock();
-    CallOrder co(s, L, p->policy.get());
-    OvlDev O{};
-    if ((r = push_map(p->lxc, s))) return r;
-    O.lx = lxc_dev(p->lxc, s);
-    const gf_node_cfg &node = node_cfg();
-    O.host_ifindex = node.host_ifindex;
-    memcpy(O.host_mac, node.host_mac, 6); memcpy(O.node_mac, node.node_mac, 6);
-    PolicyPass pass;
-    const uint32_t trace = (p->cfg.flags & GF_OVERLAY_F_TRACE_NOTIFY) ? (TR_FROM_OVERLAY | (GF_STAGE_OVERLAY << 8)) : 0u;
-    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, pass, trace, p->cfg.ingress_ifindex, O.vec_copy,
-                      O.tcap_in, "k_ovl_front",
-                      [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
-        if (geneve)
-            launch_nt(k_ovl_front<256, true>, k_ovl_front<128, true>, f, fr, b->tunnel_id, b->tc_index, O, slot_of, rec,
-                      keys, f.s6, f.d6, out, snap_out, f.sink, f.K, G);
-        else
-            launch_nt(k_ovl_front<256, false>, k_ovl_front<128, false>, f, fr, b->tunnel_id, b->tc_index, O, slot_of, rec,
-                      keys, f.s6, f.d6, out, snap_out, f.sink, f.K, OvlOpt<false>{});
-    });
-}
-
-int gf_overlay_classify(int ovl, const gf_overlay_batch *b, uint32_t now_sec, gf_pipeline_out *out,
-                        uint8_t *snap_out, void *stream) {
-    return overlay_call(ovl, b, nullptr, false, now_sec, out, snap_out, stream);
-}
-
-int gf_overlay_classify_opts(int ovl, const gf_overlay_batch *b, const gf_tunnel_opts *opts, uint32_t now_sec,
-                             gf_pipeline_out *out, uint8_t *snap_out, void *stream) {
-    return overlay_call(ovl, b, opts, true, now_sec, out, snap_out, stream);
-}
-
-// ---- encap_and_redirect's tunnel metadata of an egress call's records ----
-int gf_lxc_egress_tunnel_meta(int policy_array, const uint16_t *lxc_id, const gf_egress_out *records, uint32_t n,
-                              uint32_t *tunnel_id, uint8_t *opt, uint8_t *opt_len, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto a = get_as<PolicyArray>(policy_array);
-    if (!a) return -EBADF;
-    if (n == 0) return 0;
-    if (!lxc_id || !records || !tunnel_id || !opt || !opt_len) return -EFAULT;
-    if ((uintptr_t)opt & 3u) return -EINVAL;           // written as two words per packet (gf_tunnel_opts' alignment)
-    if (n > (1u << 30)) return -E2BIG;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    std::lock_guard<std::mutex> ag(a->mu);
-    MapLocks L;                                        // prog_table pushes the programs' maps
-    lock_array_maps(L, a);
-    L.lock();
-    CallOrder co(s, L, a.get());
-    int r;
-    std::vector<std::shared_ptr<ProgLxc>> progs;
-    if ((r = prog_table(a, s, progs))) return r;
-    ProfScope ps("k_tun_meta", s);
-    hipLaunchKernelGGL(k_tun_meta, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, lxc_id, records, n,
-                       (const uint16_t *)a->d_slot_of_lxc.p, (const gf_lxc_dev *)a->d_cfgs.p, tunnel_id,
-                       reinterpret_cast<uint32_t *>(opt), opt_len);
-    return hip_ok(hipGetLastError(), "k_tun_meta");
-}
-
-// ---- from-host ----
-int gf_host_load(const gf_host_cfg *cfg) {
-    std::unique_lock<std::shared_mutex> g(prog_lock());
-    if (!cfg) return -EFAULT;
-    auto p = std::make_shared<ProgHost>();
-    p->cfg = *cfg;
-    auto m = get_map(cfg->netdev.lxc_map);
-    if (!m) return -EBADF;
-    if (!lxc_map_ok(*m)) return -EINVAL;
-    p->lxc = m;
-    p->policy = get_as<PolicyArray>(cfg->policy_array);
-    if (!p->policy) return -EBADF;
-    return new_handle(p);
-}
-
-int gf_host_classify(int host, const gf_host_batch *b, uint32_t now_sec, gf_pipeline_out *out,
-                     uint8_t *snap_out, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgHost>(host);
-    if (!p) return -EBADF;
-    if (!b) return -EFAULT;
-    const gf_frames &fr = b->frames;
-    int r = frames_check(fr, out != nullptr);
-    if (r <= 0) return r;
-    hipStream_t s = (hipStream_t)stream;
-    HostMarks hm;
-    CtxScope cx(s);
-    std::lock_guard<std::mutex> ag(p->policy->mu);
-    // cilium_proxy{4,6}, the tunnel map and the node's cilium_lxc are among the array's
-    // maps: the front reads them under the locks ingress_run writes them under
-    MapLocks L;
-    L.add(p->lxc);
-    lock_array_maps(L, p->policy);
-    L.lock();
-    CallOrder co(s, L, p->policy.get());
-    HostDev H{};
-    auto px4 = proxy_map(4), px6 = proxy_map(6), tun = node_map(2);
-    if ((r = push_map(p->lxc, s)) || (r = push_map(px4, s)) || (r = push_map(px6, s)) || (r = push_map(tun, s))) return r;
-    const gf_netdev_cfg &nd = p->cfg.netdev;
-    H.lx = lxc_dev(p->lxc, s);
-    H.enc = encap_dev(node_cfg(), tun, s);
-    if (px4) H.px4 = px4->hdesc();
-    if (px6) H.px6 = px6->hdesc();
-    H.flags = nd.flags; H.fixed_secctx = nd.fixed_secctx;
-    memcpy(H.router6, nd.router_ip6, 8);
-    memcpy(H.net_mac, p->cfg.cilium_net_mac, 6);
-    PolicyPass pass;
-    pass.keep_flags = true;
-    pass.hmark = b->mark;
-    const uint32_t trace = (nd.flags & GF_NETDEV_F_TRACE_NOTIFY) ? (TR_FROM_HOST | (GF_STAGE_HOST << 8)) : 0u;
-    return front_call(p->policy, fr, b->flow_hash, now_sec, out, snap_out, s, pass, trace, nd.ingress_ifindex, H.vec_copy,
-                      H.tcap_in, "k_host_front",
-                      [&](const FrontLaunch &f, const uint16_t *slot_of, gf_rec *rec, uint32_t *keys) {
-        launch_nt(k_host_front<256>, k_host_front<128>, f, fr, b->mark, b->tc_index, H, slot_of, rec, keys, f.s6, f.d6, out,
-                  snap_out, f.sink, f.K);
-    });
-}
-
-// ---- ingest re-partition ----
-int gf_pipeline_partition(int pipe, const gf_pipe_batch *b, uint32_t self_rank, uint32_t nranks, uint32_t *owner,
-                          uint32_t *order, uint32_t *counts, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto p = get_as<ProgPipe>(pipe);
-    if (!p) return -EBADF;
-    if (!b || !owner || !order || !counts) return -EFAULT;
-    if (nranks == 0 || nranks > 65536 || self_rank >= nranks) return -EINVAL;
-    const gf_frames &fr = b->frames;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    MapLocks L;
-    if (p->lb) { L.add(p->lb->lb4); L.add(p->lb->lb6); }
-    L.lock();
-    CallOrder co(s, L);
-    if (hip_ok(hipMemsetAsync(counts, 0, (size_t)nranks * 4, s), "partition counts")) return -EIO;
-    if (fr.n == 0) return 0;
-    if (!fr.snap || !fr.len) return -EFAULT;
-    if (fr.snap_stride < 14) return -EINVAL;
-    if (fr.n > (1u << 30)) return -E2BIG;
-    int r;
-    PipeDev P{};
-    if (p->lb) {
-        if ((r = push_map(p->lb->lb4, s)) || (r = push_map(p->lb->lb6, s))) return r;
-        P.L = lb_dev(*p->lb);
-        P.has_lb = 1;
-    }
-    const uint32_t n = fr.n;
-    struct PartWs { DevBuf keys, tmp; };
-    static const char tag = 0;
-    PartWs &pw = cur_ctx().get<PartWs>(&tag);
-    DevBuf &keys = pw.keys, &tmp = pw.tmp;
-    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
-    if ((r = grow(keys, (size_t)n * 4))) return r;
-    {
-        ProfScope ps("k_partition", s);
-        hipLaunchKernelGGL(k_partition, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, fr, b->flow_hash, P, self_rank,
-                           nranks, owner, counts);
-        if ((r = hip_ok(hipGetLastError(), "k_partition"))) return r;
-    }
-    // stable counting order by owner: radix sort of (owner, index) over the owner's bits
-    int bits = 1;
-    while ((1u << bits) < nranks) bits++;
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, tb, owner, (uint32_t *)keys.p, rocprim::counting_iterator<uint32_t>(0u), order,
-                                    n, 0, bits, s);
-    if ((r = grow(tmp, tb + 256))) return r;
-    tb = tmp.bytes;
-    if (hip_ok(rocprim::radix_sort_pairs(tmp.p, tb, owner, (uint32_t *)keys.p, rocprim::counting_iterator<uint32_t>(0u),
-                                         order, n, 0, bits, s), "partition sort"))
-        return -EIO;
-    return 0;
-}
-
-// ---- conntrack GC ----
-// The test gf_ct_gc and gf_ct_gc_maps apply to a handle's map: a CT map by its sizes.
-static bool ct_gc_accepts(const Map &m) { return !m.is_lpm() && (m.ksz == 14 || m.ksz == 40) && m.vsz == 48; }
-// A map whose host shadow is authoritative (the caller holds its lock): delete there, the
-// replica is rebuilt on the next push.  Returns the entries deleted.
-static bool ct_gc_on_host(const Map &m) { return m.host_valid || !m.dev_valid || !m.d_slots.p; }
-static uint64_t ct_gc_host(Map &m, uint32_t filter_time) {
-    if (m.ht.slots.empty()) return 0;                   // never materialised: no entries
-    const uint32_t lt_off = m.ht.codec == GF_VCODEC_CT ? 0u : 32u;
-    uint64_t dead = 0;
-    std::vector<std::string> keys;
-    uint8_t v[GF_CT_VSZ];
-    for (uint64_t i = 0; i < m.ht.nslots; i++) {
-        if (m.ht.state(i) != GF_SLOT_FULL) continue;
-        m.ht.get_val(i, v);
-        uint32_t lt;
-        memcpy(&lt, v + lt_off, 4);
-        if (lt < filter_time) keys.emplace_back((const char *)m.ht.key(i), m.ksz);
-    }
-    for (auto &k : keys) if (m.erase((const uint8_t *)k.data()) == 0) dead++;
-    return dead;
-}
-int gf_ct_gc(int map, uint32_t filter_time, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto m = get_map(map);
-    if (!m) return -EBADF;
-    if (!ct_gc_accepts(*m)) return -EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    std::lock_guard<std::recursive_mutex> mg(m->mu);
-    CallOrder co(s, std::vector<OrderPt *>{&m->ord});
-    if (ct_gc_on_host(*m)) return (int)std::min<uint64_t>(ct_gc_host(*m, filter_time), 0x7fffffff);
-    LruDev *L;
-    uint32_t *bits;
-    int rr;
-    if ((rr = ct_sweep_bufs(*m, L, bits))) return rr;
-    GcCut cut{filter_time, filter_time, 1u, 0u};             // lifetime < filter_time
-    const unsigned long long zero2[2] = {0, 0};
-    if (hip_ok(hipMemcpyAsync(&L->cut, &cut, sizeof cut, hipMemcpyHostToDevice, s), "gc cut") ||
-        hip_ok(hipMemcpyAsync(L->res, zero2, sizeof zero2, hipMemcpyHostToDevice, s), "gc res"))
-        return -EIO;
-    {
-        ProfScope ps("k_gc", s);
-        ct_sweep_launch(*m, L, bits, s);
-    }
-    if (hip_ok(hipGetLastError(), "k_gc")) return -EIO;
-    unsigned long long r[2] = {0, 0};
-    const GcCut off{0, 0, 0u, 0u};
-    if (hip_ok(hipMemcpyAsync(r, L->res, 16, hipMemcpyDeviceToHost, s), "gc result") ||
-        hip_ok(hipMemcpyAsync(&L->cut, &off, sizeof off, hipMemcpyHostToDevice, s), "gc cut off") ||
-        hip_ok(hipStreamSynchronize(s), "gc sync"))
-        return -EIO;
-    // device element count: entries are deleted, tombstones were already uncounted
-    uint32_t cnt = 0;
-    if (hip_ok(hipMemcpy(&cnt, m->d_count.p, 4, hipMemcpyDeviceToHost), "gc count")) return -EIO;
-    cnt = cnt >= r[0] ? cnt - (uint32_t)r[0] : 0u;
-    if (hip_ok(hipMemcpy(m->d_count.p, &cnt, 4, hipMemcpyHostToDevice), "gc count")) return -EIO;
-    m->dev_count_hi = cnt;
-    m->ev_pending = 0;
-    m->st_floor = m->lru_seq;
-    m->device_modified();
-    return (int)std::min<unsigned long long>(r[0], 0x7fffffff);
-}
-
-// One GC round over many CT maps (EnableConntrackGC, pkg/endpointmanager/conntrack.go:84-130:
-// every endpoint's local pair and the global pair): the outcome of gf_ct_gc on each map,
-// with one validation, one set of locks (MapLocks, address order), one CallOrder, and for
-// the device-owned maps GF_GC_MULTI maps per chain of three launches (k_gc_*_multi), the
-// counts fixed on the device and one readback of every map's result row.
-int gf_ct_gc_maps(const int *maps, uint32_t n, uint32_t filter_time, uint32_t *deleted, void *stream) {
-    if (n == 0) return 0;
-    if (!maps) return -EFAULT;
-    if (n > 65536u) return -E2BIG;
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    std::vector<std::shared_ptr<Map>> ms(n);
-    for (uint32_t k = 0; k < n; k++) {
-        if (!(ms[k] = get_map(maps[k]))) return -EBADF;
-        if (!ct_gc_accepts(*ms[k])) return -EINVAL;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    MapLocks ml;
-    for (auto &m : ms) ml.add(m);
-    ml.lock();
-    if (ml.held.size() != n) return -EINVAL;            // the same map object twice (lock() drops duplicates)
-    CallOrder co(s, ml);
-    // the device-owned maps' buffers first: a failure here has touched no map
-    std::vector<uint32_t> dev;
-    for (uint32_t k = 0; k < n; k++) {
-        if (ct_gc_on_host(*ms[k])) continue;
-        LruDev *L;
-        uint32_t *bits;
-        int rr;
-        if ((rr = ct_sweep_bufs(*ms[k], L, bits))) return rr;
-        dev.push_back(k);
-    }
-    struct GcWs { DevBuf res; std::vector<unsigned long long> h; };
-    static const char tag = 0;
-    GcWs &w = cur_ctx().get<GcWs>(&tag);
-    const size_t row = 4 * sizeof(unsigned long long);
-    if (!dev.empty() && w.res.bytes < dev.size() * row) {
-        size_t cap = 64;
-        while (cap < dev.size()) cap *= 2;
-        if (w.res.ensure(cap * row)) return -ENOMEM;
-    }
-    std::vector<unsigned long long> cnt(n, 0ull);
-    for (uint32_t k = 0; k < n; k++)
-        if (ct_gc_on_host(*ms[k])) cnt[k] = ct_gc_host(*ms[k], filter_time);
-    if (!dev.empty()) {
-        unsigned long long *res = (unsigned long long *)w.res.p;
-        if (hip_ok(hipMemsetAsync(res, 0, dev.size() * row, s), "gc rows")) return -EIO;
-        {
-            ProfScope ps("k_gc_multi", s);
-            for (size_t b = 0; b < dev.size(); b += GF_GC_MULTI) {
-                GcBatch B{};
-                B.n = (uint32_t)std::min<size_t>(GF_GC_MULTI, dev.size() - b);
-                uint64_t tiles = 0;
-                for (uint32_t j = 0; j < B.n; j++) {
-                    Map &m = *ms[dev[b + j]];
-                    GcMap &M = B.m[j];
-                    M.d = m.hdesc();
-                    M.bits = (uint32_t *)m.d_gcbits.p;
-                    M.res = res + 4 * (b + j);
-                    M.mode = m.ht.mode;
-                    M.lt_off = m.ht.codec == GF_VCODEC_CT ? 0u : 32u;
-                    B.t0[j] = (uint32_t)tiles;
-                    tiles += ((M.d.mask + 1 + 31) / 32 + BLOCK - 1) / BLOCK;
-                }
-                if (tiles > 0xffffffffull) return -E2BIG;   // (2^45 slots: no such tables)
-                B.t0[B.n] = (uint32_t)tiles;
-                const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, 65535u * 8);
-                hipLaunchKernelGGL(k_gc_starts_multi, dim3(grid), dim3(BLOCK), 0, s, B);
-                hipLaunchKernelGGL(k_gc_clusters_multi, dim3(grid), dim3(BLOCK), 0, s, B, filter_time);
-                hipLaunchKernelGGL(k_gc_end_multi, dim3(1), dim3(64), 0, s, B);
-            }
-        }
-        if (hip_ok(hipGetLastError(), "k_gc_multi")) return -EIO;
-        w.h.resize(dev.size() * 4);
-        if (hip_ok(hipMemcpyAsync(w.h.data(), res, dev.size() * row, hipMemcpyDeviceToHost, s), "gc rows back") ||
-            hip_ok(hipStreamSynchronize(s), "gc sync"))
-            return -EIO;
-        for (size_t j = 0; j < dev.size(); j++) {
-            Map &m = *ms[dev[j]];
-            cnt[dev[j]] = w.h[4 * j];
-            m.dev_count_hi = w.h[4 * j + 2];            // exact: k_gc_end_multi left the count there
-            m.ev_pending = 0;
-            m.st_floor = m.lru_seq;
-            m.device_modified();
-        }
-    }
-    unsigned long long sum = 0;
-    for (uint32_t k = 0; k < n; k++) {
-        sum += cnt[k];
-        if (deleted) deleted[k] = (uint32_t)std::min<unsigned long long>(cnt[k], 0xffffffffull);
-    }
-    return (int)std::min<unsigned long long>(sum, 0x7fffffff);
-}
-
-// ---- proxy map GC / redirect-close cleanup ----
-// Both states of a map, as gf_ct_gc: on the host shadow while it is authoritative (no
-// launch, no device needed), else a sweep of the HBM replica.  After the sweep the
-// device count drops by the entries deleted and the host's bound of it (dev_count_hi,
-// which px_log_apply only ever raises) is that exact count, so the next proxy log is
-// applied in parallel again whenever count + log <= max_entries.
-static int px_gc(int map, const PxGcPred &pred_of_v4, const PxGcPred &pred_of_v6, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto m = get_map(map);
-    if (!m) return -EBADF;
-    const bool v4 = m->ksz == 10 && m->vsz == 16, v6 = m->ksz == 22 && m->vsz == 28;
-    if (m->is_lpm() || (!v4 && !v6)) return -EINVAL;
-    const PxGcPred P = v4 ? pred_of_v4 : pred_of_v6;
-    hipStream_t s = (hipStream_t)stream;
-    CtxScope cx(s);
-    std::lock_guard<std::recursive_mutex> mg(m->mu);
-    CallOrder co(s, std::vector<OrderPt *>{&m->ord});
-    if (m->host_valid || !m->dev_valid || !m->d_slots.p) {
-        if (m->ht.slots.empty()) return 0;              // never materialised: no entries
-        uint64_t dead = 0;
-        std::vector<std::string> keys;
-        uint8_t v[28];
-        for (uint64_t i = 0; i < m->ht.nslots; i++) {
-            if (m->ht.state(i) != GF_SLOT_FULL) continue;
-            const uint8_t *k = m->ht.key(i);
-            bool kill;
-            if (P.mode == GF_PXGC_LIFETIME) {
-                m->ht.get_val(i, v);
-                uint32_t lt;
-                memcpy(&lt, v + P.off, 4);
-                kill = lt < P.arg;
-            } else {
-                uint16_t dp;
-                memcpy(&dp, k + P.off, 2);
-                kill = dp == P.arg && k[P.nh_off] == 6;
-            }
-            if (kill) keys.emplace_back((const char *)k, m->ksz);
-        }
-        for (auto &k : keys) if (m->erase((const uint8_t *)k.data()) == 0) dead++;
-        return (int)std::min<uint64_t>(dead, 0x7fffffff);
-    }
-    struct PxGcWs { DevBuf st; };
-    static const char tag = 0;
-    DevBuf &st = cur_ctx().get<PxGcWs>(&tag).st;
-    if (!st.p && st.ensure(sizeof(PxGcDev))) return -ENOMEM;
-    const size_t nw = (m->ht.nslots + 31) / 32;
-    if (m->d_gcbits.bytes < nw * 4 && m->d_gcbits.ensure(nw * 4)) return -ENOMEM;
-    PxGcDev *D = (PxGcDev *)st.p;
-    uint32_t *bits = (uint32_t *)m->d_gcbits.p;
-    PxGcDev init{};
-    init.on.active = 1u;
-    if (hip_ok(hipMemcpyAsync(D, &init, sizeof init, hipMemcpyHostToDevice, s), "proxy gc init")) return -EIO;
-    {
-        ProfScope ps("k_px_gc", s);
-        const gf_htab_desc d = m->hdesc();
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((nw + BLOCK - 1) / BLOCK, 65535u * 8);
-        hipLaunchKernelGGL(k_gc_starts, dim3(grid), dim3(BLOCK), 0, s, d, bits, (const GcCut *)&D->on);
-        hipLaunchKernelGGL(k_px_gc, dim3(grid), dim3(BLOCK), 0, s, d, P, (const uint32_t *)bits, D->res);
-    }
-    if (hip_ok(hipGetLastError(), "k_px_gc")) return -EIO;
-    unsigned long long r[2] = {0, 0};
-    if (hip_ok(hipMemcpyAsync(r, D->res, 16, hipMemcpyDeviceToHost, s), "proxy gc result") ||
-        hip_ok(hipStreamSynchronize(s), "proxy gc sync"))
-        return -EIO;
-    uint32_t cnt = 0;
-    int rr;
-    if ((rr = m->dev_count(cnt))) return rr;
-    cnt = cnt >= r[0] ? cnt - (uint32_t)r[0] : 0u;
-    if ((rr = m->dev_set_count(cnt))) return rr;        // the device count and dev_count_hi, both exact
-    m->device_modified();
-    return (int)std::min<unsigned long long>(r[0], 0x7fffffff);
-}
-
-int gf_proxy_gc(int map, uint32_t filter_time, void *stream) {
-    return px_gc(map, PxGcPred{GF_PXGC_LIFETIME, filter_time, 12u, 0u}, PxGcPred{GF_PXGC_LIFETIME, filter_time, 24u, 0u}, stream);
-}
-
-int gf_proxy_cleanup_port(int map, uint16_t dport, void *stream) {
-    return px_gc(map, PxGcPred{GF_PXGC_PORT, dport, 4u, 8u}, PxGcPred{GF_PXGC_PORT, dport, 16u, 20u}, stream);
-}
-
-#if GF_WRSTATS
-// Diagnostic builds only: the write-source counters (gf_device.h WR_*), read and cleared.
-int gf_diag_wrstats(unsigned long long *out, uint32_t n) {
-    if (hip_ok(hipDeviceSynchronize(), "wrstats sync")) return -EIO;
-    unsigned long long v[WR_N] = {0};
-    if (hip_ok(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_wrstat), sizeof v), "wrstats")) return -EIO;
-    const unsigned long long z[WR_N] = {0};
-    if (hip_ok(hipMemcpyToSymbol(HIP_SYMBOL(g_wrstat), z, sizeof z), "wrstats clear")) return -EIO;
-    for (uint32_t k = 0; k < n && k < WR_N; k++) out[k] = v[k];
-    return WR_N;
-}
-#endif
-
-int gf_ct_evict_log(int map, gf_ct_evict_rec *out, uint32_t max) {
-    auto m = get_map(map);
-    if (!m) return -EBADF;
-    if (max && !out) return -EFAULT;
-    std::lock_guard<std::recursive_mutex> mg(m->mu);
-    if (!m->d_lru.p) return 0;
-    static_assert(sizeof(LruLog) == sizeof(gf_ct_evict_rec), "log record layout");
-    if (hip_ok(hipDeviceSynchronize(), "evict log sync")) return -EIO;
-    uint32_t n = 0;
-    LruDev *L = (LruDev *)m->d_lru.p;
-    if (hip_ok(hipMemcpy(&n, &L->nlog, 4, hipMemcpyDeviceToHost), "evict log count")) return -EIO;
-    const uint32_t k = std::min(std::min(n, GF_LRU_LOGCAP), max);
-    if (k && hip_ok(hipMemcpy(out, L->log, (size_t)k * sizeof(LruLog), hipMemcpyDeviceToHost), "evict log")) return -EIO;
-    return (int)std::min<uint32_t>(n, 0x7fffffffu);
-}
-
-}  // extern "C"
+// ---- host: the entry points over ingress_run, and the CT / proxy GC calls ----
+#include "gf_host_entry.h"
 
 
-// ================================================================ bulk insert (gf_map_update_batch)
-// A batch of distinct keys loaded straight into a fixed-capacity table in HBM:
-// one lane per element walks the key's probe sequence, overwrites the key's slot
-// (BPF_ANY) or claims the first EMPTY slot with a CAS on its state word (BUSY),
-// fills key and value and publishes FULL with a release store; readers acquire
-// the state word first.  Keys are distinct (checked first), so the outcome is
-// that of the sequential updates.
-__device__ __forceinline__ void bulk_key_words(const uint8_t *k, uint32_t ksz, uint32_t *kw) {
-    for (int q = 0; q < 16; q++) kw[q] = 0;
-    for (uint32_t b = 0; b < ksz; b++) kw[b >> 2] |= (uint32_t)k[b] << (8 * (b & 3));
-}
-__device__ __forceinline__ bool bulk_eq(const uint8_t *a, const uint8_t *b, uint32_t n) {
-    for (uint32_t q = 0; q < n; q++) if (a[q] != b[q]) return false;
-    return true;
-}
-__global__ __launch_bounds__(BLOCK) void k_bulk_hash(const uint8_t *keys, uint32_t ksz, uint32_t mode, uint32_t n, uint32_t *h) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        uint32_t kw[16];
-        bulk_key_words(keys + (size_t)i * ksz, ksz, kw);
-        h[i] = gf_key_hash(kw, ksz, mode);
-    }
-}
-// flag[0]: two equal keys in the batch (equal keys have equal hashes: adjacent runs after the sort)
-__global__ __launch_bounds__(BLOCK) void k_bulk_dups(const uint32_t *hs, const uint32_t *idx, const uint8_t *keys,
-                                                     uint32_t ksz, uint32_t n, uint32_t *flag) {
-    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
-        for (int64_t k = (int64_t)j - 1; k >= 0 && hs[k] == hs[j]; k--)
-            if (bulk_eq(keys + (size_t)idx[k] * ksz, keys + (size_t)idx[j] * ksz, ksz)) atomicOr(&flag[0], 1u);
-}
-__device__ __forceinline__ uint32_t bulk_state_word(const gf_htab_desc &d, uint64_t j) {
-    const uint32_t *sw = reinterpret_cast<const uint32_t *>(d.slots + j * d.slot_size + (d.ksz & ~3u));
-    return __hip_atomic_load(sw, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-}
-// flag[1]: a key of the batch is already in the table
-__global__ __launch_bounds__(BLOCK) void k_bulk_probe(gf_htab_desc d, const uint8_t *keys, const uint32_t *h, uint32_t n,
-                                                      uint32_t *flag) {
-    const uint32_t sb = 8 * (d.ksz & 3u);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint8_t *k = keys + (size_t)i * d.ksz;
-        uint64_t j = gf_home_slot(h[i], d.mask, d.slot_size);
-        for (uint64_t p = 0; p <= d.mask; p++, j = (j + 1) & d.mask) {
-            const uint32_t st = (bulk_state_word(d, j) >> sb) & 0xffu;
-            if (st == GF_SLOT_EMPTY) break;
-            if (st == GF_SLOT_FULL && bulk_eq(d.slots + j * d.slot_size, k, d.ksz)) { atomicOr(&flag[1], 1u); break; }
-        }
-    }
-}
-__global__ __launch_bounds__(BLOCK) void k_bulk_insert(gf_htab_desc d, uint32_t codec, const uint8_t *keys,
-                                                       const uint8_t *vals, const uint32_t *h, uint32_t n) {
-    const uint32_t sb = 8 * (d.ksz & 3u), kw0 = d.ksz & ~3u;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const uint8_t *k = keys + (size_t)i * d.ksz, *ext = vals + (size_t)i * d.vsz;
-        uint8_t in[128];
-        if (codec == GF_VCODEC_CT) gf_ct_encode(ext, in);
-        else if (codec == GF_VCODEC_POL) gf_pol_encode(ext, in);
-        else for (uint32_t b = 0; b < d.vsz; b++) in[b] = ext[b];
-        uint32_t keep = 0;
-        for (uint32_t b = kw0; b < d.ksz; b++) keep |= (uint32_t)k[b] << (8 * (b - kw0));
-        auto put_val = [&](uint64_t j) {
-            uint8_t *sl = d.slots + j * d.slot_size;
-            for (uint32_t b = 0; b < d.vin; b++) sl[d.voff + b] = in[b];
-            for (uint32_t b = d.vin; b < d.vsz; b++) d.vals[j * d.sstride + (b - d.vin)] = in[b];
-        };
-        uint64_t j = gf_home_slot(h[i], d.mask, d.slot_size);
-        for (uint64_t p = 0; p <= d.mask;) {
-            uint32_t *sw = reinterpret_cast<uint32_t *>(d.slots + j * d.slot_size + kw0);
-            uint32_t w = bulk_state_word(d, j);
-            const uint32_t st = (w >> sb) & 0xffu;
-            if (st == GF_SLOT_FULL && bulk_eq(d.slots + j * d.slot_size, k, d.ksz)) { put_val(j); break; }
-            if (st == GF_SLOT_EMPTY) {
-                const uint32_t busy = keep | ((uint32_t)GF_SLOT_BUSY << sb);
-                uint32_t seen = w;
-                __hip_atomic_compare_exchange_strong(sw, &seen, busy, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT);
-                if (seen != w) continue;                       // lost the slot: look at it again
-                uint8_t *sl = d.slots + j * d.slot_size;
-                for (uint32_t b = 0; b < kw0; b++) sl[b] = k[b];
-                put_val(j);
-                __hip_atomic_store(sw, keep | ((uint32_t)GF_SLOT_FULL << sb), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                atomicAdd(d.count, 1u);
-                break;
-            }
-            p++;
-            j = (j + 1) & d.mask;
-        }
-    }
-}
+// ---- the maps' bulk paths: k_bulk_*, gf_map_update_batch; k_dump_gather, gf_map_lookup_batch ----
+#include "gf_map_bulk.h"
 
-namespace gf {
-int dev_bulk_insert(Map &m, const uint8_t *keys, const uint8_t *vals, uint32_t n, uint64_t flags, bool &fallback) {
-    fallback = true;
-    int dc = 0;
-    if (hipGetDeviceCount(&dc) != hipSuccess || dc == 0 || m.vsz > 128 || m.ksz > 64) return 0;
-    const bool had = m.dev_auth();
-    uint64_t before = 0;
-    if (had) { uint32_t c; if (m.dev_count(c)) return 0; before = c; }
-    if (before + n > dev_insert_limit(m)) return 0;     // the host path reports E2BIG at the exact element
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    static DevBuf dk, dv, dh, dhs, didx, tmp, dflag;
-    auto grow = [](DevBuf &b, size_t want) -> int { return b.bytes >= want ? 0 : b.ensure(want); };
-    int r;
-    if ((r = grow(dk, (size_t)n * m.ksz)) || (r = grow(dv, (size_t)n * m.vsz)) || (r = grow(dh, (size_t)n * 4)) ||
-        (r = grow(dhs, (size_t)n * 4)) || (r = grow(didx, (size_t)n * 4)) || (r = grow(dflag, 8)))
-        return r;
-    if (!had) {                                          // create the (empty) replica
-        m.dev_valid = false;
-        if ((r = m.push((hipStream_t)0))) return r;
-    }
-    const hipStream_t s = (hipStream_t)0;
-    if (hip_ok(hipMemcpy(dk.p, keys, (size_t)n * m.ksz, hipMemcpyHostToDevice), "bulk keys") ||
-        hip_ok(hipMemcpy(dv.p, vals, (size_t)n * m.vsz, hipMemcpyHostToDevice), "bulk vals") ||
-        hip_ok(hipMemset(dflag.p, 0, 8), "bulk flags"))
-        return -EIO;
-    m.xfer_h2d += (size_t)n * (m.ksz + m.vsz);
-    const gf_htab_desc d = m.hdesc();
-    const uint32_t g = std::min<uint32_t>((n + BLOCK - 1) / BLOCK, 65535u);
-    hipLaunchKernelGGL(k_bulk_hash, dim3(g), dim3(BLOCK), 0, s, (const uint8_t *)dk.p, m.ksz, m.ht.mode, n, (uint32_t *)dh.p);
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)dh.p, (uint32_t *)dhs.p, rocprim::counting_iterator<uint32_t>(0u),
-                                    (uint32_t *)didx.p, n, 0, 32, s);
-    if ((r = grow(tmp, tb + 256))) return r;
-    tb = tmp.bytes;
-    if (hip_ok(rocprim::radix_sort_pairs(tmp.p, tb, (uint32_t *)dh.p, (uint32_t *)dhs.p, rocprim::counting_iterator<uint32_t>(0u),
-                                         (uint32_t *)didx.p, n, 0, 32, s), "bulk sort"))
-        return -EIO;
-    hipLaunchKernelGGL(k_bulk_dups, dim3(g), dim3(BLOCK), 0, s, (const uint32_t *)dhs.p, (const uint32_t *)didx.p,
-                       (const uint8_t *)dk.p, m.ksz, n, (uint32_t *)dflag.p);
-    if (had && flags == GF_NOEXIST)
-        hipLaunchKernelGGL(k_bulk_probe, dim3(g), dim3(BLOCK), 0, s, d, (const uint8_t *)dk.p, (const uint32_t *)dh.p, n,
-                           (uint32_t *)dflag.p);
-    uint32_t fl[2] = {0, 0};
-    if (hip_ok(hipGetLastError(), "bulk check") || hip_ok(hipMemcpy(fl, dflag.p, 8, hipMemcpyDeviceToHost), "bulk flags"))
-        return -EIO;
-    if (fl[0] || fl[1]) return 0;                        // duplicates / EEXIST: the sequential host path
-    hipLaunchKernelGGL(k_bulk_insert, dim3(g), dim3(BLOCK), 0, s, d, m.ht.codec, (const uint8_t *)dk.p,
-                       (const uint8_t *)dv.p, (const uint32_t *)dh.p, n);
-    if (hip_ok(hipGetLastError(), "k_bulk_insert") || hip_ok(hipDeviceSynchronize(), "bulk sync")) return -EIO;
-    m.host_valid = false;
-    m.dev_gen++;
-    m.dev_count_hi = before + n;
-    m.ev_pending = 0;
-    m.st_floor = m.lru_seq;
-    fallback = false;
-    return 0;
-}
-}  // namespace gf
-
-// ================================================================ chunked dump (gf_map_lookup_batch)
-// The FULL slots of a range of a device-authoritative hash map, compacted in
-// slot order on the device (rocPRIM select over the slot indices), their keys
-// and reference-layout values gathered into a staging buffer: only the entries
-// cross PCIe, a 64M-entry CT dumps without its 16 GB slot arrays moving.
-struct SlotFull {
-    const uint8_t *slots;
-    uint64_t base;
-    uint32_t ss, ksz;
-    __device__ bool operator()(uint32_t j) const { return slots[(base + j) * ss + ksz] == GF_SLOT_FULL; }
-};
-__global__ __launch_bounds__(BLOCK) void k_dump_gather(gf_htab_desc d, uint32_t codec, uint64_t base, const uint32_t *sel,
-                                                       const uint32_t *nsel, uint32_t cap, uint8_t *keys, uint8_t *vals) {
-    const uint32_t n = min(*nsel, cap);
-    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        const uint64_t i = base + sel[t];
-        const uint8_t *sl = d.slots + i * d.slot_size;
-        for (uint32_t b = 0; b < d.ksz; b++) keys[(size_t)t * d.ksz + b] = sl[b];
-        uint8_t in[128], ext[128];
-        for (uint32_t b = 0; b < d.vin; b++) in[b] = sl[d.voff + b];
-        for (uint32_t b = d.vin; b < d.vsz; b++) in[b] = d.vals[i * d.sstride + (b - d.vin)];
-        if (codec == GF_VCODEC_CT) gf_ct_decode(in, ext);
-        else if (codec == GF_VCODEC_POL) gf_pol_decode(in, ext);
-        else for (uint32_t b = 0; b < d.vsz; b++) ext[b] = in[b];
-        for (uint32_t b = 0; b < d.vsz; b++) vals[(size_t)t * d.vsz + b] = ext[b];
-    }
-}
-
-namespace gf {
-int dev_dump(Map &m, uint64_t start, uint32_t max, uint8_t *keys, uint8_t *vals, uint32_t *n, uint64_t *next) {
-    static std::mutex mu;                                // the staging buffers below
-    std::lock_guard<std::mutex> g(mu);
-    static DevBuf sel, nsel, tmp, dk, dv;
-    *n = 0; *next = start;
-    if (!max || start >= m.ht.nslots) { *next = m.ht.nslots; return 0; }
-    if (m.vsz > 128) return -EOPNOTSUPP;
-    const uint64_t R = std::min<uint64_t>(m.ht.nslots - start, std::min<uint64_t>(1ull << 24, std::max<uint64_t>(1ull << 16, 4ull * max)));
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(max, R);
-    auto grow = [](DevBuf &b, size_t want) -> int { return b.bytes >= want ? 0 : b.ensure(want); };
-    int r;
-    if ((r = grow(sel, R * 4)) || (r = grow(nsel, 8)) || (r = grow(dk, (size_t)cap * m.ksz)) || (r = grow(dv, (size_t)cap * m.vsz)))
-        return r;
-    gf_htab_desc d = m.hdesc();
-    SlotFull pred{d.slots, start, d.slot_size, d.ksz};
-    size_t tb = 0;
-    (void)rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0u), (uint32_t *)sel.p, (uint32_t *)nsel.p,
-                          (size_t)R, pred, (hipStream_t)0);
-    if ((r = grow(tmp, tb + 256))) return r;
-    tb = tmp.bytes;
-    if (hip_ok(rocprim::select(tmp.p, tb, rocprim::counting_iterator<uint32_t>(0u), (uint32_t *)sel.p, (uint32_t *)nsel.p,
-                               (size_t)R, pred, (hipStream_t)0), "dump select"))
-        return -EIO;
-    const uint32_t g2 = (uint32_t)std::min<uint64_t>((cap + BLOCK - 1) / BLOCK, 65535u);
-    hipLaunchKernelGGL(k_dump_gather, dim3(g2 ? g2 : 1), dim3(BLOCK), 0, (hipStream_t)0, d, m.ht.codec, start,
-                       (const uint32_t *)sel.p, (const uint32_t *)nsel.p, cap, (uint8_t *)dk.p, (uint8_t *)dv.p);
-    if (hip_ok(hipGetLastError(), "k_dump_gather")) return -EIO;
-    uint32_t ns = 0;
-    if (hip_ok(hipMemcpy(&ns, nsel.p, 4, hipMemcpyDeviceToHost), "dump count")) return -EIO;
-    const uint32_t got = std::min(ns, cap);
-    m.xfer_d2h += 4 + (size_t)got * (m.ksz + m.vsz);
-    if (got && (hip_ok(hipMemcpy(keys, dk.p, (size_t)got * m.ksz, hipMemcpyDeviceToHost), "dump keys") ||
-                hip_ok(hipMemcpy(vals, dv.p, (size_t)got * m.vsz, hipMemcpyDeviceToHost), "dump vals")))
-        return -EIO;
-    if (ns > cap) {                                      // stopped inside the range: resume after the last one
-        uint32_t last = 0;
-        if (hip_ok(hipMemcpy(&last, (const uint32_t *)sel.p + (cap - 1), 4, hipMemcpyDeviceToHost), "dump last")) return -EIO;
-        *next = start + last + 1;
-    } else {
-        *next = start + R;
-    }
-    *n = got;
-    return 0;
-}
-}  // namespace gf
-
-// ---- endpoint egress (from-container) ----
-namespace {
-struct EgWs { DevBuf erec, rec2, key2, seq, ctlog, ctlog_n, snap, ckey, s6, d6,
-             hzk, hzfl, hztk, hztf, hzak, hzaf, hzst, vip4, vip6, keysP, key2P, rlog, rlog_n, v6blk,
-             rsslot, rslist;
-             uint32_t hz_gen = 0, hz_cap = 0;
-             uint32_t *h_hz = nullptr;          // pinned: the ordering check's words, read back without a stream sync
-             hipEvent_t ev_hz = nullptr;
-             std::vector<std::pair<const Map *, uint64_t>> vip_stamp;
-             uint32_t vip4_mask = 0, vip6_mask = 0; bool vip4_any = false, vip6_any = false; };
-EgWs &eg_ws() { static const char tag = 0; return cur_ctx().get<EgWs>(&tag); }
-}  // namespace
-
-static int egress_ordered(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                          gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru, uint32_t first, uint32_t depth);
-static int egress_runs(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                       gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru, const std::vector<uint32_t> &cut);
-static int egress_each(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                       gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru) {
-    std::vector<uint32_t> cut(b->frames.n + 1);
-    for (uint32_t j = 0; j <= b->frames.n; j++) cut[j] = j;
-    return egress_runs(a, b, now_sec, out, snap_out, s, lru, cut);
-}
-// The rev-NAT addresses of the programs' revNAT maps as device sets (the ordering
-// check's GF_HZ_VIP), rebuilt when a map changed through the API.
-static int vip_sets(const std::vector<std::shared_ptr<ProgLxc>> &progs, EgWs &ew, hipStream_t s) {
-    std::vector<std::pair<const Map *, uint64_t>> stamp;
-    std::vector<Map *> m4, m6;
-    for (auto &p : progs) {
-        if (p->revnat4 && std::find(m4.begin(), m4.end(), p->revnat4.get()) == m4.end()) m4.push_back(p->revnat4.get());
-        if (p->revnat6 && std::find(m6.begin(), m6.end(), p->revnat6.get()) == m6.end()) m6.push_back(p->revnat6.get());
-    }
-    for (Map *m : m4) stamp.push_back({m, m->host_gen * 2});
-    for (Map *m : m6) stamp.push_back({m, m->host_gen * 2 + 1});
-    if (stamp == ew.vip_stamp) return 0;                // (no maps and nothing built compare equal too)
-    std::vector<uint32_t> a4;
-    std::vector<std::array<uint32_t, 4>> a6;
-    std::vector<uint8_t> v(32);
-    for (int fam = 4; fam <= 6; fam += 2) {
-        for (Map *m : fam == 4 ? m4 : m6) {
-            std::lock_guard<std::recursive_mutex> g(m->mu);
-            int r = m->pull();
-            if (r) return r;
-            for (uint64_t i = 0; i < m->ht.nslots; i++) {
-                if (m->ht.state(i) != GF_SLOT_FULL) continue;
-                m->ht.get_val(i, v.data());
-                if (fam == 4) { uint32_t x; memcpy(&x, v.data(), 4); if (x) a4.push_back(x); }
-                else { std::array<uint32_t, 4> x; memcpy(x.data(), v.data(), 16); if (x[0] | x[1] | x[2] | x[3]) a6.push_back(x); }
-            }
-        }
-    }
-    auto build = [&](size_t cnt, uint32_t &mask) { mask = 15; while ((uint64_t)mask + 1 < 4ull * cnt) mask = mask * 2 + 1; };
-    ew.vip4_any = !a4.empty(); ew.vip6_any = !a6.empty();
-    if (ew.vip4_any) {
-        build(a4.size(), ew.vip4_mask);
-        std::vector<uint32_t> t(ew.vip4_mask + 1, 0);
-        for (uint32_t x : a4) {
-            uint32_t slot = vip_slot(x) & ew.vip4_mask;
-            while (t[slot] && t[slot] != x) slot = (slot + 1u) & ew.vip4_mask;
-            t[slot] = x;
-        }
-        if (ew.vip4.ensure(t.size() * 4) ||
-            hip_ok(hipMemcpyAsync(ew.vip4.p, t.data(), t.size() * 4, hipMemcpyHostToDevice, s), "vip4") ||
-            hip_ok(hipStreamSynchronize(s), "vip4 sync"))
-            return -EIO;
-    }
-    if (ew.vip6_any) {
-        build(a6.size(), ew.vip6_mask);
-        std::vector<std::array<uint32_t, 4>> t(ew.vip6_mask + 1, std::array<uint32_t, 4>{0, 0, 0, 0});
-        for (auto &x : a6) {
-            uint32_t slot = vip_slot(x[0] ^ vip_slot(x[1] ^ vip_slot(x[2] ^ vip_slot(x[3])))) & ew.vip6_mask;
-            while ((t[slot][0] | t[slot][1] | t[slot][2] | t[slot][3]) && t[slot] != x) slot = (slot + 1u) & ew.vip6_mask;
-            t[slot] = x;
-        }
-        if (ew.vip6.ensure(t.size() * 16) ||
-            hip_ok(hipMemcpyAsync(ew.vip6.p, t.data(), t.size() * 16, hipMemcpyHostToDevice, s), "vip6") ||
-            hip_ok(hipStreamSynchronize(s), "vip6 sync"))
-            return -EIO;
-    }
-    ew.vip_stamp = stamp;
-    return 0;
-}
-// The per-call words of egress_call in one launch instead of four fills: the
-// sequence words (seq[1] the ordering check's flag, seq[3] its first hazard,
-// ~0 = none), both log counts and the front's scratch counter block.
-__global__ __launch_bounds__(256) void k_eg_init(uint32_t *seq, uint32_t *ctlog_n, uint32_t *rlog_n,
-                                                 unsigned long long *hzst) {
-    const uint32_t t = threadIdx.x;
-    if (t < 3) seq[t] = 0u;
-    if (t == 3) seq[3] = ~0u;
-    if (t < 2) ctlog_n[t] = 0u;
-    if (t < 2 && rlog_n) rlog_n[t] = 0u;
-    if (hzst)
-        for (uint32_t k = t; k < 272; k += 256) hzst[k] = 0ull;
-}
-// A log of deferred CT4 writes {order, key[4], value[12], pad[3]} applied in
-// order (k_ctlog_max / k_ctlog_apply: the last writer of a key wins).
-// nlog: an upper bound of the entry count (*d_n, read by the kernels): no host
-// round trip for the count.
-// cfgs (per-endpoint CT maps): each entry into its program's own map instead of ct.
-static int ctlog_apply(EgWs &ew, const uint32_t *lg, const uint32_t *d_n, uint32_t nlog, const gf_htab_desc &ct,
-                       uint32_t *ct_count, hipStream_t s, const gf_lxc_dev *cfgs = nullptr) {
-    if (!nlog) return 0;
-    uint32_t cap = 1023;                               // the set for the bound, at <= 1/2 load
-    while ((uint64_t)cap + 1 < 2ull * nlog) cap = cap * 2 + 1;
-    const size_t tb = (size_t)(cap + 1) * 8;
-    if (ew.ckey.bytes < tb) {                           // a new set: zero once (k_ctlog_apply keeps it zero)
-        if (ew.ckey.ensure(tb)) return -ENOMEM;
-        if (hip_ok(hipMemsetAsync(ew.ckey.p, 0, tb, s), "ct log set")) return -EIO;
-    }
-    ProfScope ps("k_ctlog_apply", s);
-    const uint32_t gs = std::min<uint32_t>((cap + BLOCK) / BLOCK, 2048u);   // grid-stride over the set
-    const uint32_t gl = (nlog + BLOCK - 1) / BLOCK;
-    if (cfgs) {
-        hipLaunchKernelGGL(k_ctlog_max<true>, dim3(gl), dim3(BLOCK), 0, s, lg, d_n, (unsigned long long *)ew.ckey.p, cap);
-        hipLaunchKernelGGL(k_ctlog_apply<true>, dim3(gs), dim3(BLOCK), 0, s, lg, d_n, (unsigned long long *)ew.ckey.p, cap,
-                           gf_htab_desc{}, nullptr, cfgs);
-    } else {
-        hipLaunchKernelGGL(k_ctlog_max<false>, dim3(gl), dim3(BLOCK), 0, s, lg, d_n, (unsigned long long *)ew.ckey.p, cap);
-        hipLaunchKernelGGL(k_ctlog_apply<false>, dim3(gs), dim3(BLOCK), 0, s, lg, d_n, (unsigned long long *)ew.ckey.p,
-                           cap, ct, ct_count, nullptr);
-    }
-    return hip_ok(hipGetLastError(), "k_ctlog_apply");
-}
-// One ordered run of an egress batch: check = run the ordering check first (a
-// flagged batch is split into runs, each through this function again); lru = the
-// LRU stand-in after it (once per classify call).
-static int egress_call(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                       gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool check, bool lru, uint32_t depth = 0) {
-    const gf_frames &fr = b->frames;
-    const uint32_t n = fr.n, S = fr.snap_stride;
-    if (n == 0) return 0;
-    check = check && n > 1;
-    int r;
-    std::vector<std::shared_ptr<ProgLxc>> progs;
-    if ((r = prog_table(a, s, progs))) return r;
-    CtMaps cm;
-    if ((r = ct_maps_of(progs, cm))) return r;
-    const bool pct = cm.pct;                           // per-endpoint CT maps (ConntrackLocal)
-    std::shared_ptr<Map> ct4m = pct ? nullptr : cm.one(4), ct6m = pct ? nullptr : cm.one(6);
-    uint32_t strict = 0;
-    gf_htab_desc cfg_ct4{}, cfg_ct6{};
-    if ((r = ct_limits(ct4m, ct6m, n, 3, s, strict, cfg_ct4, cfg_ct6))) return r;
-    if (pct && (r = ct_limits_pct(cm, n, 3, s, strict))) return r;   // a family's bit: one of its maps could fill
-    auto lxc = node_map(1), tun = node_map(2);
-    if ((r = push_map(lxc, s)) || (r = push_map(tun, s))) return r;
-    EgWs &ew = eg_ws();
-    auto grow = [](DevBuf &d, size_t want) -> int { return d.bytes >= want ? 0 : d.ensure(want); };
-    uint32_t hmask = 1023, amask = 1023;                 // conn keys at <= 1/2 load, up to 4 aux keys at <= 1/2
-    while (check && (uint64_t)hmask + 1 < 2ull * n) hmask = hmask * 2 + 1;
-    while (check && (uint64_t)amask + 1 < 8ull * n) amask = amask * 2 + 1;
-    if ((r = grow(ew.erec, (size_t)n * sizeof(EgRec))) || (r = grow(ew.rec2, (size_t)n * sizeof(gf_rec))) ||
-        (r = grow(ew.key2, (size_t)n * 4)) || (r = grow(ew.seq, 16)) || (r = grow(ew.ctlog_n, 8)) ||
-        (r = grow(ew.ctlog, (size_t)n * GF_CTLOG_WORDS * 4)) || (r = grow(ew.s6, (size_t)n * 32)) || (r = grow(ew.hzst, 272 * 8)) || (r = ws_grow(n)))
-        return r;
-    if (check && ((r = grow(ew.hzk, (size_t)n * 8 * GF_HZ_NK)) || (r = grow(ew.hzfl, (size_t)n)) ||
-                  (r = grow(ew.hztk, (size_t)(hmask + 1) * 8)) || (r = grow(ew.hztf, (size_t)(hmask + 1) * 16)) ||
-                  (r = grow(ew.hzak, (size_t)(amask + 1) * 8)) || (r = grow(ew.hzaf, (size_t)(amask + 1) * 8))))
-        return r;
-    // In place (snap_out == the frames) with the check: the flagged pass must leave
-    // the frames as they came, so the rewrites go to scratch and are copied at the end
-    // (also when tracing: TRACE_FROM_LXC captures the frames as sent).
-    PolicyPass pass;                                    // the deliveries' handle_policy pass, below
-    pass.kind = PassKind::Egress;
-    pass.on = event_ring().records && array_traces(a);
-    pass.orig = fr.snap; pass.lxc_id = b->lxc_id;
-    if (pass.on && (r = trace_prepare(n, false, s))) return r;
-    const bool inplace = (check || pass.on) && snap_out == fr.snap;
-    uint8_t *wsnap = inplace ? nullptr : snap_out;
-    if (!wsnap) {
-        if ((r = grow(ew.snap, (size_t)n * S))) return r;
-        wsnap = (uint8_t *)ew.snap.p;
-    }
-    const gf_node_cfg &node = node_cfg();
-    EgDev E{};
-    E.cfgs = (const gf_lxc_dev *)a->d_cfgs.p;
-    E.slot_of = (const uint16_t *)a->d_slot_of_lxc.p;
-    E.K = gf_key_for(n);
-    E.ct4 = cfg_ct4; E.ct6 = cfg_ct6;
-    if ((r = grow(ew.v6blk, (n + BLOCK - 1) / BLOCK))) return r;
-    E.v6blk = (uint8_t *)ew.v6blk.p;
-    E.s6out = (uint8_t *)ew.s6.p; E.d6out = (uint8_t *)ew.s6.p + 16;   // interleaved (IngCtx::a6_stride 32)
-    memcpy(E.router6, node.router_ip6, 16); memcpy(E.host6, node.host_ip6, 16);
-    if (lxc) {
-        E.lxc = lxc->hdesc();
-        front_addr_set(lxc, s, E.lxset, E.lxbits, E.lxzero);
-    }
-    if (tun) {
-        E.tunnel = tun->hdesc();
-        front_addr_set(tun, s, E.tnset, E.tnbits, E.tnzero);
-    }
-    E.snap = wsnap; E.stride = S; E.now = now_sec; E.host_ifindex = host_ifindex();
-    E.encap_ifindex = node.encap_ifindex;
-    E.cluster_range = node.ipv4_cluster_range; E.cluster_mask = node.ipv4_cluster_mask;
-    E.loopback = node.ipv4_loopback; E.ipv4_mask = node.ipv4_mask;
-    memcpy(E.host_mac, node.host_mac, 6);
-    E.strict = strict;
-    E.seq = (uint32_t *)ew.seq.p;
-    E.ctlog = (uint32_t *)ew.ctlog.p; E.ctlog_n = (uint32_t *)ew.ctlog_n.p;
-    E.rec2 = (gf_rec *)ew.rec2.p; E.key2 = (uint32_t *)ew.key2.p;
-    // Connection groups for IPv4 (EgDev::conn): off when CT4 inserts are counted
-    // exactly (strict: the batch runs as one bucket anyway).
-    static const bool no_conn = getenv("GF_EG_PAIRS") != nullptr;   // diagnosis: address-pair groups only
-    const bool conn = ct4m && !(strict & 1u) && !no_conn;
-    uint32_t *d_rn = nullptr;                          // [0] related entries logged, [1] pair-group fallback
-    if (conn) {
-        // the related entries' set (RelSet): 4n slots keep it at most half full (<= 2n
-        // writes, one per new connection in each pass); batches too large for 32-bit slot
-        // numbers keep the write log
-        uint64_t ns = 1024;
-        while (ns < 4ull * n) ns *= 2;
-        const bool rset = ns <= (1ull << 31);
-        if ((r = grow(ew.keysP, (size_t)n * 4)) || (r = grow(ew.key2P, (size_t)n * 4)) || (r = grow(ew.rlog_n, 8)) ||
-            (!rset && (r = grow(ew.rlog, (size_t)2 * n * GF_CTLOG_WORDS * 4))))
-            return r;
-        d_rn = (uint32_t *)ew.rlog_n.p;
-        E.conn = 1; E.cflag = d_rn + 1;
-        E.keysP = (uint32_t *)ew.keysP.p; E.key2P = (uint32_t *)ew.key2P.p;
-        E.rlog = (uint32_t *)ew.rlog.p; E.rlog_n = d_rn;
-        if (rset) {
-            // zeroed when allocated, and left zero by k_rset_apply, which clears every
-            // slot a run claimed
-            const size_t sb = (size_t)(ns + 1) * 16;
-            if (ew.rsslot.bytes < sb) {
-                if (ew.rsslot.ensure(sb)) return -ENOMEM;
-                if (hip_ok(hipMemsetAsync(ew.rsslot.p, 0, sb, s), "related set")) return -EIO;
-            }
-            if ((r = grow(ew.rslist, (size_t)2 * n * 4 + 4))) return r;
-            E.rs.slot = (unsigned long long *)ew.rsslot.p;
-            E.rs.list = (uint32_t *)ew.rslist.p; E.rs.list_n = d_rn; E.rs.mask = (uint32_t)(ns - 1);
-            E.rlog = E.rs.list;                          // (marks the set in use for the deliveries' pass)
-        }
-    }
-    uint32_t *d_hz = (uint32_t *)ew.seq.p + 1;           // word 1 of the seq buffer: the hazard flag
-    if (check) {
-        E.hz_k = (uint64_t *)ew.hzk.p; E.hz_fl = (uint8_t *)ew.hzfl.p; E.hz = d_hz;
-        if ((r = vip_sets(progs, ew, s))) return r;
-        if (ew.vip4_any) { E.vip4 = (const uint32_t *)ew.vip4.p; E.vip4_mask = ew.vip4_mask; }
-        if (ew.vip6_any) { E.vip6 = (const uint4 *)ew.vip6.p; E.vip6_mask = ew.vip6_mask; }
-    }
-    E.X.snap = nullptr; E.X.snap_stride = S; E.X.now = now_sec; E.X.gw = node.ipv4_gateway;   // writes: k_eg_groups
-    memcpy(E.X.host6, node.host_ip6, 16);
-    if (pass.on) { E.X.tmark = (uint8_t *)trace_ws().mark.p; E.X.tcap = (uint8_t *)trace_ws().px.p; }
-    if ((r = px_log_begin(n, s, E.X))) return r;
-    unsigned long long *sink = (unsigned long long *)stats_sink();
-    // With the check, the front counts into a scratch block folded into the sink
-    // only when the batch runs as it is (a flagged batch's runs count themselves).
-    unsigned long long *fsink = sink;
-    if (check && sink) fsink = (unsigned long long *)ew.hzst.p;
-    hipLaunchKernelGGL(k_eg_init, dim3(1), dim3(256), 0, s, (uint32_t *)ew.seq.p, (uint32_t *)ew.ctlog_n.p, d_rn,
-                       fsink != sink ? fsink : nullptr);
-    Workspace &w = ws();
-    {
-        ProfScope ps("k_eg_front", s);
-        // the IPv4 kernel's LDS rows: one per lane, the staged header bytes (<= GF_EG_STAGE)
-        const uint32_t eg_lds = BLOCK * std::min<uint32_t>(S, GF_EG_STAGE);
-        hipLaunchKernelGGL(k_eg_front<4>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), eg_lds, s, fr, b->lxc_id, b->flow_hash,
-                           E, (EgRec *)ew.erec.p, (uint32_t *)w.keys.p, out, fsink);
-        hipLaunchKernelGGL(k_eg_front<6>, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 16, s, fr, b->lxc_id, b->flow_hash,
-                           E, (EgRec *)ew.erec.p, (uint32_t *)w.keys.p, out, fsink);
-        hipLaunchKernelGGL(k_eg_seq_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint32_t *)ew.seq.p,
-                           (const uint32_t *)E.cflag, (const uint32_t *)E.keysP, n, (uint32_t *)w.keys.p, E.K);
-        if ((r = hip_ok(hipGetLastError(), "k_eg_front"))) return r;
-    }
-    if (check) {
-        ProfScope ps("k_hz_check", s);
-        if (ew.hz_cap != hmask + 1 || ew.hz_gen >= 0xffffu) {   // new table or wrapped generation
-            if (hip_ok(hipMemsetAsync(ew.hztk.p, 0, (size_t)(hmask + 1) * 8, s), "hz keys") ||
-                hip_ok(hipMemsetAsync(ew.hztf.p, 0, (size_t)(hmask + 1) * 16, s), "hz first"))
-                return -EIO;
-            ew.hz_cap = hmask + 1; ew.hz_gen = 0;
-        }
-        const HzGen C{(unsigned long long *)ew.hztk.p, (unsigned long long *)ew.hztf.p, hmask, ++ew.hz_gen};
-        const HzTab A{(unsigned long long *)ew.hzak.p, (uint32_t *)ew.hzaf.p, amask};
-        hipLaunchKernelGGL(k_hz_clear, dim3(std::min<uint32_t>((amask + 1) / BLOCK, 8192)), dim3(BLOCK), 0, s, A,
-                           (const uint32_t *)d_hz);
-        hipLaunchKernelGGL(k_hz_insert, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint64_t *)ew.hzk.p,
-                           (const uint8_t *)ew.hzfl.p, n, (const uint32_t *)d_hz, C, A);
-        hipLaunchKernelGGL(k_hz_probe, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint64_t *)ew.hzk.p,
-                           (const uint8_t *)ew.hzfl.p, n, C, A, strict, d_hz);
-        if ((r = hip_ok(hipGetLastError(), "k_hz_check"))) return r;
-        // the check's verdict goes to pinned host memory behind an event: the host
-        // reads it while the device already builds the schedule (no stream sync)
-        if (!ew.h_hz && (hip_ok(hipHostMalloc((void **)&ew.h_hz, 16, hipHostMallocDefault), "hz host") ||
-                         hip_ok(hipEventCreateWithFlags(&ew.ev_hz, hipEventDisableTiming), "hz event")))
-            return -EIO;
-        if (hip_ok(hipMemcpyAsync(ew.h_hz, d_hz, 12, hipMemcpyDeviceToHost, s), "hz flag") ||
-            hip_ok(hipEventRecord(ew.ev_hz, s), "hz record"))
-            return -EIO;
-    }
-    if ((r = schedule_groups(n, s, true))) return r;   // (reads only the front's keys: harmless on a flagged batch)
-    host_mark("front+sched");
-    // k_eg_groups is queued before the host looks at the ordering check: it reads the
-    // check's flag itself and idles on a flagged batch (no map state changes then), so
-    // the device has the schedule and the groups to run while the host waits for the
-    // check's verdict and enqueues the rest of the call behind them
-    {
-        const uint32_t grid = std::min(resident_blocks(8), (n + BLOCK - 1) / BLOCK);
-        ProfScope ps("k_eg_groups", s);
-        // one launch per family: IPv4 stages one header row per lane in LDS (eg_row_bytes of the snap
-        // stride), IPv6 none; the count word is the family's CT map's, null with per-endpoint maps
-        // (pct: each packet's change goes to its own program's map)
-        auto launch = [&](auto k4, auto k6) {
-            auto go = [&](auto kern, size_t lds, const std::shared_ptr<Map> &ct) {
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, s, E, (uint32_t *)w.sched.p, (const uint2 *)w.order.p,
-                                   (const uint32_t *)w.perm.p, (const EgRec *)ew.erec.p, out, (gf_rec *)ew.rec2.p,
-                                   (uint32_t *)ew.key2.p, ct ? (uint32_t *)ct->d_count.p : nullptr, sink);
-            };
-            go(k4, BLOCK * eg_row_bytes(S), ct4m);
-            go(k6, 16, ct6m);
-        };
-        if (pct) launch(k_eg_groups<4, true>, k_eg_groups<6, true>);
-        else launch(k_eg_groups<4>, k_eg_groups<6>);
-        if ((r = hip_ok(hipGetLastError(), "k_eg_groups"))) return r;
-    }
-    uint32_t hz = 0, hz_first = 0;
-    if (check) {
-        if (hip_ok(hipEventSynchronize(ew.ev_hz), "hz sync")) return -EIO;
-        host_mark("hzwait");
-        hz = ew.h_hz[0]; hz_first = ew.h_hz[2];
-    }
-    if (hz & 2u) {
-        if (getenv("GF_HZ_DEBUG")) fprintf(stderr, "[gf] egress n=%u: a CT map could fill, one packet at a time\n", n);
-        return egress_each(a, b, now_sec, out, snap_out, s, lru);
-    }
-    if (hz) return egress_ordered(a, b, now_sec, out, snap_out, s, lru, hz_first, depth);
-    // ct_create4's deferred service entries, in batch order; every count from here
-    // on is read on the device (no host round trip inside the call)
-    if (check && sink) {
-        hipLaunchKernelGGL(k_stats_fold, dim3(1), dim3(256), 0, s, (const unsigned long long *)fsink, sink);
-        if ((r = hip_ok(hipGetLastError(), "k_stats_fold"))) return r;
-    }
-    if (ct4m && (r = ctlog_apply(ew, (const uint32_t *)ew.ctlog.p, (const uint32_t *)ew.ctlog_n.p, n, cfg_ct4,
-                                 (uint32_t *)ct4m->d_count.p, s)))
-        return r;
-    if (pct && !cm.m4.empty() &&
-        (r = ctlog_apply(ew, (const uint32_t *)ew.ctlog.p, (const uint32_t *)ew.ctlog_n.p, n, gf_htab_desc{}, nullptr, s,
-                         (const gf_lxc_dev *)a->d_cfgs.p)))
-        return r;
-    for (auto *v : {&cm.m4, &cm.m6})
-        for (auto &m : *v) m->device_modified();
-    // The egress redirects' cilium_proxy{4,6} updates stay in the log: the
-    // deliveries' handle_policy appends theirs and the whole log is applied in
-    // packet order after it (nothing on these paths reads the proxy maps).
-    // handle_policy of the local deliveries (the tail calls of ipv4_local_delivery)
-    gf_pkt_cols c2{};
-    c2.n = n;
-    c2.len = fr.len;
-    c2.flow_hash = b->flow_hash;
-    c2.saddr6 = (const uint8_t *)ew.s6.p; c2.daddr6 = (const uint8_t *)ew.s6.p + 16;   // IPv6 deliveries (if any)
-    // the deliveries' keys: their connections, or address pairs when the run fell back
-    // k_eg_groups wrote them in batch order: they become the workspace's records and
-    // keys by exchanging the buffers (the workspace's old ones are the next call's
-    // pass-2 buffers), not by copying n records; a fallen-back run takes the pair
-    // keys on the device (k_eg_seq_keys' rule, *cflag)
-    pass.pack = [&](const uint16_t *, gf_rec *, uint32_t *) -> int {
-        Workspace &w = ws();
-        std::swap(w.rec.p, ew.rec2.p); std::swap(w.rec.bytes, ew.rec2.bytes);
-        std::swap(w.keys.p, ew.key2.p); std::swap(w.keys.bytes, ew.key2.bytes);
-        if (conn) {
-            hipLaunchKernelGGL(k_eg_pick_keys, dim3(grid_for(n)), dim3(BLOCK), 0, s, (const uint32_t *)E.cflag,
-                               (const uint32_t *)ew.key2P.p, n, (uint32_t *)w.keys.p);
-            return hip_ok(hipGetLastError(), "k_eg_pick_keys");
-        }
-        return 0;
-    };
-    if (conn) { pass.rlog = E.rlog; pass.rlog_n = d_rn; pass.rlog_off = E.cflag; pass.rs = E.rs; }
-    pass.pout = (uint8_t *)out;
-    pass.ev_len = fr.len;
-    pass.ev_snap = wsnap;
-    pass.ev_stride = S;
-    pass.wsnap = wsnap;
-    pass.lru = lru && !conn;                            // (with connection groups: after the related entries, below)
-    pass.px_keep = true;                                // the from-container pass' redirects are in the log
-    if ((r = ingress_run(a, &c2, now_sec, s, pass))) return r;
-    if (conn && E.rs.slot) {                           // both passes' related entries: each key's last writer
-        ProfScope ps("k_ctlog_apply", s);
-        // the deliveries' records are the workspace's now (the pack swap above)
-        hipLaunchKernelGGL(k_rset_apply, dim3(std::min<uint32_t>(grid_for(2 * n), 2048u)), dim3(BLOCK), 0, s, E.rs,
-                           (const EgRec *)ew.erec.p, (const gf_rec *)ws().rec.p, E.cfgs, cfg_ct4,
-                           (uint32_t *)ct4m->d_count.p, now_sec);
-        if ((r = hip_ok(hipGetLastError(), "k_rset_apply"))) return r;
-    } else if (conn) {                                 // both passes' related entries, in packet order
-        if ((r = ctlog_apply(ew, (const uint32_t *)ew.rlog.p, d_rn, 2 * n, cfg_ct4, (uint32_t *)ct4m->d_count.p, s)))
-            return r;
-    }
-    if (conn) {
-        ct4m->device_modified();
-        if (lru && ((r = lru_evict(ct4m, now_sec, s)) || (r = lru_evict(ct6m, now_sec, s)))) return r;
-    }
-    static const bool logstats = getenv("GF_EG_LOGSTATS") != nullptr;   // diagnostics: syncs the stream
-    if (logstats) {
-        uint32_t c[2] = {0, 0}, rc[2] = {0, 0};
-        if (!hip_ok(hipStreamSynchronize(s), "logstats") &&
-            !hip_ok(hipMemcpy(c, ew.ctlog_n.p, 8, hipMemcpyDeviceToHost), "logstats") &&
-            (!conn || !hip_ok(hipMemcpy(rc, d_rn, 8, hipMemcpyDeviceToHost), "logstats")))
-            fprintf(stderr, "[gf] egress n=%u: service-entry log %u, related-entry log %u (fallback %u)\n", n, c[0], rc[0],
-                    rc[1]);
-    }
-    if (inplace && hip_ok(hipMemcpyAsync(snap_out, wsnap, (size_t)n * S, hipMemcpyDeviceToDevice, s), "snap copy"))
-        return -EIO;
-    return 0;
-}
-
-// A flagged batch: the cut points (a new run starts at a packet whose reverse
-// direction is in the current run, and around every single-bucket tuple), then
-// every run through egress_call in order.  Nothing of the flagged pass changed
-// the maps: k_eg_groups idled, and the front only reads them.
-static int egress_greedy(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                         gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru);
-static int egress_ordered(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                          gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru, uint32_t first, uint32_t depth) {
-    const uint32_t n = b->frames.n;
-    if (getenv("GF_HZ_DEBUG")) fprintf(stderr, "[gf] egress n=%u: ordering hazard at %u (run %u)\n", n, first, depth + 1);
-    if (first == 0 || first >= n || depth >= 32) return egress_greedy(a, b, now_sec, out, snap_out, s, lru);
-    // [0, first) has no hazard; the rest runs after it, checked again
-    std::vector<uint32_t> cut{0, first};
-    int r = egress_runs(a, b, now_sec, out, snap_out, s, false, cut);
-    if (r) return r;
-    const uint32_t S = b->frames.snap_stride;
-    gf_lxc_batch rest = *b;
-    rest.frames.n = n - first;
-    rest.frames.snap = b->frames.snap + (size_t)first * S;
-    rest.frames.len = b->frames.len + first;
-    if (b->lxc_id) rest.lxc_id = b->lxc_id + first;
-    if (b->flow_hash) rest.flow_hash = b->flow_hash + first;
-    return egress_call(a, &rest, now_sec, out + first, snap_out ? snap_out + (size_t)first * S : nullptr, s, true, lru,
-                       depth + 1);
-}
-// Many runs: the cut points on the host, in one pass over the batch's keys.
-static int egress_greedy(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                         gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru) {
-    EgWs &ew = eg_ws();
-    const uint32_t n = b->frames.n;
-    std::vector<uint64_t> K((size_t)n * GF_HZ_NK);
-    std::vector<uint8_t> fl(n);
-    if (hip_ok(hipMemcpyAsync(K.data(), ew.hzk.p, K.size() * 8, hipMemcpyDeviceToHost, s), "hz keys") ||
-        hip_ok(hipMemcpyAsync(fl.data(), ew.hzfl.p, n, hipMemcpyDeviceToHost, s), "hz fl") ||
-        hip_ok(hipStreamSynchronize(s), "hz sync"))
-        return -EIO;
-    // the rules of k_hz_insert / k_hz_probe over the current run (keys are odd:
-    // bit 0 carries a connection key's direction)
-    std::vector<uint32_t> cut{0};
-    std::unordered_set<uint64_t> seen;
-    const uint64_t D = 1ull;
-    uint32_t why[5] = {0, 0, 0, 0, 0};
-    auto k = [&](uint32_t which, uint32_t j) { return K[(size_t)which * n + j] & ~D; };
-    for (uint32_t j = 0; j < n; j++) {
-        const uint32_t f = fl[j];
-        if (!(f & GF_HZ_VALID)) continue;
-        const bool h0 = seen.count(k(1, j) | ((f & GF_HZ_DIRE) ? 0ull : D)) != 0;
-        const bool h1 = (f & GF_HZ_ICMP) && seen.count(k(3, j) ^ 2ull) != 0;
-        const bool h2 = seen.count((k(3, j) ^ GF_HZ_ICMPSALT) & ~D) != 0;
-        const bool h3 = (f & GF_HZ_LOOP) && (seen.count(k(0, j)) || seen.count(k(0, j) | D));
-        const bool h4 = (f & GF_HZ_VIP) && seen.count(k(4, j) ^ 2ull) != 0;
-        why[0] += h0; why[1] += h1; why[2] += h2; why[3] += h3; why[4] += h4;
-        if (h0 || h1 || h2 || h3 || h4) { cut.push_back(j); seen.clear(); }
-        if (f & GF_HZ_DLV) seen.insert(k(0, j) | ((f & GF_HZ_DIRI) ? D : 0ull));
-        seen.insert(k(2, j) ^ 2ull);
-        if (f & GF_HZ_ICMP) seen.insert((k(2, j) ^ GF_HZ_ICMPSALT) & ~D);
-        seen.insert(k(4, j) ^ 2ull);
-        seen.insert(k(5, j) ^ 2ull);
-    }
-    if (cut.back() != n) cut.push_back(n);
-    if (getenv("GF_HZ_DEBUG"))
-        fprintf(stderr, "[gf] egress n=%u: %zu ordered runs (reply %u, icmp-after %u, after-icmp %u, loopback %u, vip %u)\n",
-                n, cut.size() - 1, why[0], why[1], why[2], why[3], why[4]);
-    return egress_runs(a, b, now_sec, out, snap_out, s, lru, cut);
-}
-
-// The runs [cut[k], cut[k+1]) of a batch through egress_call, in order; the LRU
-// stand-in after the last.
-static int egress_runs(const std::shared_ptr<PolicyArray> &a, const gf_lxc_batch *b, uint32_t now_sec,
-                       gf_egress_out *out, uint8_t *snap_out, hipStream_t s, bool lru, const std::vector<uint32_t> &cut) {
-    const uint32_t S = b->frames.snap_stride;
-    for (size_t k = 0; k + 1 < cut.size(); k++) {
-        const uint32_t lo = cut[k], hi = cut[k + 1];
-        gf_lxc_batch sub = *b;
-        sub.frames.n = hi - lo;
-        sub.frames.snap = b->frames.snap + (size_t)lo * S;
-        sub.frames.len = b->frames.len + lo;
-        if (b->lxc_id) sub.lxc_id = b->lxc_id + lo;
-        if (b->flow_hash) sub.flow_hash = b->flow_hash + lo;
-        int r = egress_call(a, &sub, now_sec, out + lo, snap_out ? snap_out + (size_t)lo * S : nullptr, s, false,
-                            lru && k + 2 == cut.size());
-        if (r) return r;
-    }
-    return 0;
-}
-
-extern "C" int gf_lxc_egress_classify(int array, const gf_lxc_batch *b, uint32_t now_sec, gf_egress_out *out,
-                                      uint8_t *snap_out, void *stream) {
-    std::shared_lock<std::shared_mutex> g(prog_lock());
-    auto a = get_as<PolicyArray>(array);
-    if (!a) return -EBADF;
-    if (!b) return -EFAULT;
-    const gf_frames &fr = b->frames;
-    if (fr.n == 0) return 0;
-    if (!fr.snap || !fr.len || !out) return -EFAULT;
-    if (fr.snap_stride < 34) return -EINVAL;           // an Ethernet + IPv4 header at least
-    if (fr.n > (1u << 30)) return -E2BIG;
-    // the from-container program without conntrack (bpf_lxc.c:429-674 over the stub ct_*) is not built
-    if (array_noct(a)) return -EOPNOTSUPP;
-    hipStream_t s = (hipStream_t)stream;
-    HostMarks hm;
-    CtxScope cx(s);
-    std::lock_guard<std::mutex> ag(a->mu);
-    MapLocks L;
-    lock_array_maps(L, a);
-    L.lock();
-    CallOrder co(s, L, a.get());
-    host_mark("locks");
-    static const bool nocheck = getenv("GF_EG_NOCHECK") != nullptr;     // diagnosis only: the unordered schedule
-    static const bool dbg = getenv("GF_HZ_DEBUG") != nullptr;
-    if (!dbg) return egress_call(a, b, now_sec, out, snap_out, s, !nocheck, true);
-    (void)hipStreamSynchronize(s);
-    auto t0 = std::chrono::steady_clock::now();
-    int r = egress_call(a, b, now_sec, out, snap_out, s, !nocheck, true);
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[gf] egress n=%u: %.3f ms\n", fr.n,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    return r;
-}
+// ---- host: from-container: EgWs, k_eg_init, egress_call, gf_lxc_egress_classify ----
+#include "gf_host_egress.h"
 
 // ---- the ARP / ICMPv6 responder tail calls: k_respond, gf_respond ----
 #include "gf_respond.h"

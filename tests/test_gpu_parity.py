@@ -788,7 +788,7 @@ def test_classify_argument_checks():
     wrong kind is -EBADF, a missing column or output -EFAULT, a batch over 2^30
     packets -E2BIG, a frame stride too short for the headers -EINVAL; an empty
     batch is 0 with null pointers.  No failed call writes an output or changes the
-    CT (gf_kernels.hip check_cols, gf_xdp_classify, gf_lb_classify,
+    CT (check_cols in gf_host_ctx.h; gf_xdp_classify, gf_lb_classify,
     gf_policy_ingress_classify, gf_pipeline_classify, gf_lxc_egress_classify)."""
     import ctypes as C
     import errno
